@@ -5,6 +5,10 @@ One "step" = one pass of the three HIP kernels over one batch whose inputs are a
 (BASELINE.json metric: sentences/sec on batched analyze(); workload = BASELINE configs[1]: 8k synthetic
 40-jamo sentences, Knlm, top-1).  Prints ONE JSON line (rank 0).  Multi-GPU: one process per GPU, each rank
 analyses its own shard of the same size (weak scaling; the path has no data-path collective).
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...); --dump-outputs DIR also writes what the last timed step computed.  Everything else the benchmark measures or
+checks (CPU baseline and roofline, the other workloads of config.also, end to end, the C-API client, the result gather) runs with --full.
 """
 import argparse
 import json
@@ -257,16 +261,76 @@ def capi_rate(model_path, workload, top_n, passes=5):
         return {"error": repr(e)[:200]}
 
 
+DUMP_TOKEN_TEXTS = 8192          # texts whose token records are written (a fixed, seeded sample of the batch)
+DUMP_BUDGET_BYTES = 60 << 20     # all arrays together, below 64 MB
+
+
+def dump_outputs(res, out_dir, seed=0x4B495749):
+    """What a caller of the timed path receives from the batch's last step (kamd_fetch), as float32 / float64 arrays under out_dir:
+    analysis_prob / analysis_tokens [texts, top-N] (the path score and token count of every analysis; NaN / -1 where a text has fewer analyses),
+    and for a fixed sample of texts (sorted indices drawn with `seed`, sample_texts.npy) every token record of every analysis, one array per field
+    (token_<field>.npy; token_text / token_analysis say where a row belongs) plus the UTF-16 code units of the token forms (token_form_utf16.npy,
+    token_form_len long each, in row order).  Two builds given the same arguments stage the same inputs: these arrays compare output for output."""
+    import ctypes as C
+    import numpy as np
+    from kiwi_amd.api import TOKEN_DTYPE
+    os.makedirs(out_dir, exist_ok=True)
+    lib, h = res.lib, res.h
+    n = res.n_texts()
+    sizes = np.array([lib.kamd_res_size(h, t) for t in range(n)], np.int64)
+    top = int(sizes.max()) if n else 0
+    prob = np.full((n, top), np.nan, np.float32)
+    ntok = np.full((n, top), -1, np.float64)
+    for t in range(n):
+        for i in range(int(sizes[t])):
+            prob[t, i] = lib.kamd_res_prob(h, t, i)
+            ntok[t, i] = lib.kamd_res_token_num(h, t, i)
+    arrays = {"analysis_prob": prob, "analysis_tokens": ntok}
+    fields = [f for f in TOKEN_DTYPE.names if f != "form_off"]      # (form_off: an offset into the result's own form buffer; the forms are written below)
+    k = min(n, DUMP_TOKEN_TEXTS)
+    while True:
+        sample = np.sort(np.random.default_rng(seed).permutation(n)[:k]).astype(np.int64)
+        rows = int(ntok[sample].clip(0).sum()) if k else 0
+        if k <= 1 or rows * (8 * (len(fields) + 2) + 64) + sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES:
+            break
+        k //= 2
+    recs, text_of, analysis_of, forms = [], [], [], []
+    for t in sample.tolist():
+        forms_p = lib.kamd_res_forms(h, t)
+        for i in range(int(sizes[t])):
+            a = res.token_array(t, i)
+            recs.append(a)
+            text_of.append(np.full(len(a), t, np.float64))
+            analysis_of.append(np.full(len(a), i, np.float64))
+            for r in a:
+                fl, fo = int(r["form_len"]), int(r["form_off"])
+                forms.append(np.frombuffer(C.string_at(forms_p + 2 * fo, 2 * fl), np.uint16) if fl else np.zeros(0, np.uint16))
+    rec = np.concatenate(recs) if recs else np.zeros(0, TOKEN_DTYPE)
+    arrays["sample_texts"] = sample.astype(np.float64)
+    arrays["token_text"] = np.concatenate(text_of) if text_of else np.zeros(0, np.float64)
+    arrays["token_analysis"] = np.concatenate(analysis_of) if analysis_of else np.zeros(0, np.float64)
+    for f in fields:
+        arrays["token_" + f] = rec[f].astype(np.float32 if rec.dtype[f].kind == "f" else np.float64)
+    arrays["token_form_utf16"] = (np.concatenate(forms) if forms else np.zeros(0, np.uint16)).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return arrays
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 100 for the headline workload c2 -- a 0.2 s timed region that a utilisation sampler can see --, 20 otherwise)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps, exactly this many (default: 400 for c2, 200 for the headline workload c2-64k, 40 otherwise -- a timed region of >= 1 s)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, help="default: c2-64k on one GPU (the >= 64k-sentence regime the north-star target is quoted on; c2 is measured beside it as config.also), "
                                                       "c4-cong on several (131 072 sentences per GPU = BASELINE config 4's 1M sentences at 8 GPUs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--kernels-only", action="store_true", help="profiler passes: only the warm-up and the timed region of the named workload (no CPU baseline, no side measurement, "
-                    "no C-API client, no end-to-end pass), so that per-kernel counters and statistics belong to this workload alone")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the sanity fetch, the CPU baseline and roofline, the other workloads (config.also), "
+                    "the end-to-end pass, the C-API client, the model's facts and (N > 1) the result gather.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (the results a caller of the path receives: "
+                    "per-analysis scores of every text, the token records of a fixed sample of texts) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) no CPU baseline and roofline")
+    ap.add_argument("--kernels-only", action="store_true", help="profiler passes: only the warm-up and the timed region of the named workload, even with --full "
+                    "(no CPU baseline, no side measurement, no C-API client, no end-to-end pass), so that per-kernel counters and statistics belong to this workload alone")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default): every rank analyses a batch of the workload's size; strong: ONE corpus split over the ranks by index (text i -> rank i %% N)")
     ap.add_argument("--no-side-models", action="store_true", help="config.also without the workloads that need another model loaded (c4-cong, c3-sbg)")
@@ -324,17 +388,11 @@ def main():
         torch.cuda.synchronize()
         dist.barrier()
 
-    tw0 = time.perf_counter()
     for _ in range(args.warmup):
         eng.run(batch)
     sync()
-    # --steps is a MINIMUM: the timed region lasts at least a second (a 20-step region of a 5 ms step is 0.1 s -- too short for a utilisation sampler, and
-    # for a stable mean); the step count actually timed is what the line reports.  Profiler passes (--kernels-only) time exactly what they were asked.
+    # exactly --steps timed steps (the defaults above give the headline workload a timed region of >= 1 s)
     steps_requested = args.steps
-    if args.warmup and not args.kernels_only:
-        est = dist.max_over_ranks((time.perf_counter() - tw0) / args.warmup, device="cuda" if world > 1 else "cpu")
-        if est > 0 and args.steps * est < 1.0:
-            args.steps = min(100000, int(1.0 / est) + 1)
     t0 = time.perf_counter()
     kt = {"scan_ms": 0.0, "lattice_ms": 0.0, "search_ms": 0.0, "finish_ms": 0.0}
     for _ in range(args.steps):
@@ -349,19 +407,27 @@ def main():
     # kamd_run searches every chunk to the end (chunks that outgrow their scratch are searched again inside it, with larger capacities): the
     # wall time above contains those extra passes, the per-kernel HIP-event durations are the first pass's
     rerun_chunks, rerun_ms = eng.reruns(batch)
+    extras = args.full and not args.kernels_only      # everything beside the headline figure
+
+    if args.dump_outputs and rank == 0:
+        res = eng.fetch(batch, top_n)      # the results of the last timed step
+        dump_outputs(res, args.dump_outputs)
+        res.close()
 
     # sanity: the staged batch really was analysed (token count > 0, no failed chunk)
-    res = eng.fetch(batch, top_n)
-    n_tok = sum(res.lib.kamd_res_token_num(res.h, i, 0) for i in range(min(256, n)))
-    assert n_tok > 0
-    summary = dist.gather_counts([n, n_tok], device="cuda" if world > 1 else "cpu")   # the only result "gather": per-rank counts
-    assert len(summary) == world
+    res = None
+    if args.full:
+        res = eng.fetch(batch, top_n)
+        n_tok = sum(res.lib.kamd_res_token_num(res.h, i, 0) for i in range(min(256, n)))
+        assert n_tok > 0
+        summary = dist.gather_counts([n, n_tok], device="cuda" if world > 1 else "cpu")   # the only result "gather": per-rank counts
+        assert len(summary) == world
 
     # The final result gather (the path's only exchange step): every rank packs its token records, the packed buffers are gathered on rank 0
     # over the process group (RCCL over xGMI; device tensors) and merged -- in input order when the corpus was split by index.  Outside the timed
     # regions above: `value` is device-resident by contract; the gather's own time is reported.
     gather = None
-    if world > 1:
+    if world > 1 and args.full:
         from kiwi_amd.api import Results
         packed = res.pack()
         sync()
@@ -380,10 +446,11 @@ def main():
         if rank == 0:
             assert merged_texts == n_job, (merged_texts, n_job)
 
-    res.close()
+    if res is not None:
+        res.close()
     batch.close()      # (the end-to-end pass below stages its own batch: a large workload does not fit the device twice)
     also = None
-    if args.workload == "c2-64k" and world == 1 and not args.limit and not args.kernels_only:
+    if args.workload == "c2-64k" and world == 1 and not args.limit and extras:
         # the other BASELINE configurations beside the headline, each with its own roofline fraction: configs[1] at its own batch size (8192 sentences:
         # the latency-bound regime), configs[4] (typo correction), configs[3]'s model and length mix on one GPU, configs[2] (SkipBigram, top-3: the
         # synthetic tables do not prune like a real model -- seconds per batch, hence a bounded sample)
@@ -394,7 +461,7 @@ def main():
     # End to end: UTF-16 strings resident on the host -> kamd_analyze_batch (host text preparation, H2D, kernels,
     # D2H, result assembly) -> packed token records resident on the host.  Timed through the C ABI on an already packed buffer.
     e2e = None
-    if not args.kernels_only:
+    if extras:
         tkw = {} if typo is None else {"typo": typo, "typo_threshold": typo_cfg[2]}
         from kiwi_amd.api import pack_texts
         flat, offs = pack_texts(shard)
@@ -440,10 +507,11 @@ def main():
             "vs_baseline": None, "dtype": "int32+f32", "data": "synthetic",
             "config": {"workload": desc, "sentences_per_gpu": n, "chunks_per_gpu": info["chunks"], "jamo_per_gpu": info["units"],
                        "parallelism": f"shard{world}", "m_jamo_per_s": info["units"] * world * args.steps / elapsed / 1e6,
-                       "model": model_facts(args.workload),
                        "kernel_ms": kt, "device_bytes": info["device_bytes"], "rerun_chunks": rerun_chunks, "rerun_ms": rerun_ms},
         }
-        if not args.no_cpu_baseline and not args.kernels_only:
+        if extras:
+            out["config"]["model"] = model_facts(args.workload)
+        if not args.no_cpu_baseline and extras:
             cb = cpu_baseline(model_path, texts, top_n=top_n, typo=typo_cfg, time_reference=world == 1, cong_global=workload_lm_mode(args.workload) == 4)
             per = cb["alg_bytes_per_sentence"]
             search_bytes = per["search"] * n
@@ -459,7 +527,7 @@ def main():
                     e2e["vs_cpu_baseline"] = e2e["value"] / cb["cpu_baseline"]["value"]
         if also is not None:
             out["config"]["also"] = also
-        if world == 1 and typo is None and not args.limit and not args.kernels_only:
+        if world == 1 and typo is None and not args.limit and extras:
             cr = capi_rate(model_path, args.workload, top_n)
             if cr is not None:
                 out["capi"] = cr

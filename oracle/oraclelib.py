@@ -22,6 +22,22 @@ def available() -> bool:
     return os.path.exists(LIB_PATH)
 
 
+TYPO_SETS_GOLDEN = os.path.join(os.path.dirname(HERE), "tests", "golden", "typo_default_sets.json")
+
+
+def default_typo_entries(set_name):
+    """Entries of a built-in typo set as refbridge.default_typo_entries returns them: from the committed fixture tests/golden/typo_default_sets.json
+    (tools/make_golden_typo_sets.py) where it holds the set, else from the reference itself."""
+    import json
+    sets = json.load(open(TYPO_SETS_GOLDEN, encoding="utf-8"))["sets"] if os.path.exists(TYPO_SETS_GOLDEN) else {}
+    if set_name in sets:
+        inf = lambda x: float("inf") if x is None else x
+        s = sets[set_name]
+        return [(o, e, inf(c), cond, dia) for o, e, c, cond, dia in s["entries"]], inf(s["continual"]), inf(s["lengthening"])
+    import refbridge
+    return refbridge.default_typo_entries(set_name)
+
+
 class OracleKiwi:
     def __init__(self, raw_model_path: str, enabled_dialects: int = 0):
         self.lib = C.CDLL(LIB_PATH)
@@ -151,8 +167,7 @@ class OracleKiwi:
         """The built-in typo set DefaultTypoSet::dialect as an OracleTypo, prepared: its entries come from the committed fixture tests/golden/typo_default_sets.json
         where present, else from the reference itself (refbridge)."""
         if getattr(self, "_dialect_typo", None) is None:
-            import refbridge
-            entries, continual, lengthening = refbridge.default_typo_entries("dialect")
+            entries, continual, lengthening = default_typo_entries("dialect")
             t = OracleTypo()
             t.update_entries(entries, continual, lengthening)
             t.prepare(True)

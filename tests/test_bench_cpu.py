@@ -20,24 +20,27 @@ import kiwi_amd.workloads as W
 orig = W.get_workload
 W.get_workload = lambda name: (lambda p, t, d: (p, t[:24], d))(*orig(name))
 import bench
-sys.argv = ["bench.py", "--steps", "2", "--warmup", "1", "--workload", "small-c2"]
+sys.argv = ["bench.py", "--steps", "2", "--warmup", "1", "--workload", "small-c2"] + sys.argv[1:]
 bench.main()
 '''
 
 
-def test_bench_main_emits_the_contract_line(tmp_path):
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "hipemu"), "-j8"], stdout=subprocess.DEVNULL)
+def _run_driver(*extra):
     env = dict(os.environ, KAMD_LIB=os.path.join(HERE, "hipemu", "_build", "libkiwi_hipemu.so"))
-    r = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT}], env=env, capture_output=True, text=True, cwd=ROOT)
+    r = subprocess.run([sys.executable, "-c", DRIVER % {"root": ROOT}] + list(extra), env=env, capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
-    out = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def test_bench_main_emits_the_contract_line(tmp_path):
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "hipemu"), "-j8"], stdout=subprocess.DEVNULL)
+    out = _run_driver("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in out, k
-    # (--steps is a minimum: the timed region lasts at least a second, the line reports the steps it timed)
-    assert out["n_gpus"] == 1 and out["steps_requested"] == 2 and out["steps"] >= 2 and out["warmup"] == 1 and out["unit"] == "sentences/s" and out["higher_is_better"] is True
-    assert out["steps"] * out["ms_per_step"] >= 999.0 or out["steps"] == 2
+    # (--steps is exactly the number of timed steps)
+    assert out["n_gpus"] == 1 and out["steps_requested"] == 2 and out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "sentences/s" and out["higher_is_better"] is True
     assert out["scaling"] == "weak" and out["vs_baseline"] is None and out["data"] == "synthetic" and "workload" in out["config"]
     assert out["value"] > 0 and abs(out["value"] - 24 * out["steps"] / (out["ms_per_step"] * out["steps"] / 1000.0)) < 1e-6 * out["value"] + 1e-9
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
@@ -46,6 +49,35 @@ def test_bench_main_emits_the_contract_line(tmp_path):
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in out["cpu_baseline"], k
     assert out["cpu_baseline"]["kind"] in ("reference", "port") and out["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full): the headline line alone, exactly --steps timed steps; --dump-outputs writes the results of the last step as
+    float32 / float64 .npy files, the same ones from run to run (same inputs, same outputs)."""
+    import numpy as np
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "hipemu"), "-j8"], stdout=subprocess.DEVNULL)
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        out = _run_driver("--dump-outputs", str(d))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "config"):
+            assert key in out, key
+        for key in ("roofline", "cpu_baseline", "e2e", "capi", "gather"):
+            assert key not in out, key
+        assert "also" not in out["config"] and "model" not in out["config"]
+        assert out["steps"] == 2 and out["higher_is_better"] is True and out["unit"] == "sentences/s" and out["dtype"] == "int32+f32"
+        assert abs(out["value"] - 24 * 2 / (out["ms_per_step"] * 2 / 1000.0)) < 1e-6 * out["value"] + 1e-9
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(f.endswith(".npy") for f in files) and sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+        assert arrays["analysis_prob"].shape == (24, 1) and np.isfinite(arrays["analysis_prob"]).all()
+        assert arrays["sample_texts"].tolist() == list(range(24))
+        n = len(arrays["token_text"])
+        assert n == arrays["analysis_tokens"].sum() > 0 and all(len(arrays[k]) == n for k in arrays if k.startswith("token_") and k != "token_form_utf16")
+        assert len(arrays["token_form_utf16"]) == arrays["token_form_len"].sum()
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][k], dumps[1][k], equal_nan=True) for k in dumps[0])
 
 
 DRIVER2 = r'''
@@ -63,7 +95,7 @@ import kiwi_amd.workloads as W
 orig = W.get_workload
 W.get_workload = lambda name: (lambda p, t, d: (p, t[:16], d))(*orig(name))
 import bench
-sys.argv = ["bench.py", "--gpus", os.environ.get("KAMD_TEST_WORLD", "2"), "--steps", "2", "--warmup", "1", "--workload", "small-c2", "--no-cpu-baseline"] + sys.argv[1:]
+sys.argv = ["bench.py", "--gpus", os.environ.get("KAMD_TEST_WORLD", "2"), "--steps", "2", "--warmup", "1", "--workload", "small-c2", "--full", "--no-cpu-baseline"] + sys.argv[1:]
 bench.main()
 '''
 

@@ -39,9 +39,10 @@ def built_model_path():
     dst = os.path.join(ROOT, "_data", "eval-built.raw")
     if not os.path.exists(dst) or os.path.getmtime(dst) < os.path.getmtime(src):
         os.makedirs(os.path.dirname(dst), exist_ok=True)
-        with lzma.open(src) as f, open(dst + ".tmp", "wb") as g:
+        tmp = f"{dst}.{os.getpid()}.tmp"      # (several test processes may unpack it at once: each writes its own copy, the rename is atomic)
+        with lzma.open(src) as f, open(tmp, "wb") as g:
             g.write(f.read())
-        os.replace(dst + ".tmp", dst)
+        os.replace(tmp, dst)
     return dst
 
 

@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd $ROOT
-timeout 900 python bench.py --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; cut -c1-600 $OUT/bench_$WL.json
+timeout 900 python bench.py --full --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err; cut -c1-600 $OUT/bench_$WL.json
 cd /tmp && export TMPDIR=/tmp
 timeout ${TO:-400} rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $ROOT/bench.py --workload $WL --steps 10 --warmup 2 --kernels-only > $OUT/trace_$WL.log 2>&1
 cp $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$WL.csv 2>/dev/null; rm -rf $OUT/trace
