@@ -160,6 +160,23 @@ size_t kamd_typo_lattices(kamd_engine_h h, kamd_typo_h t, float threshold, int a
 size_t kamd_dump_dict(kamd_engine_h h, uint8_t* out, size_t cap);
 size_t kamd_dump_lattices(kamd_engine_h h, const uint16_t* text, uint32_t len, uint64_t match_options, uint8_t* out, size_t cap);
 
+/* CoNgram embedding queries, batched (the kiwi_cong_* functions of kiwi_capi.h are single-query forms of these).  Ids are the language model's ids.
+ * Every call returns < 0 + kamd_last_error() on failure, also for an engine whose model is not a CoNgram one.  Results are ordered by score
+ * descending, then id ascending.  kind: 0 similar words, 1 similar contexts, 2 next words from a context, 3 the same from the difference of
+ * context ids[q] and bg_ids[q] with weight weights[q] (bg_ids / weights are read for kind 3 only). */
+int kamd_cong_info(kamd_engine_h h, uint32_t* vocab, uint32_t* contexts, uint32_t* dim);
+/* n queries; query q writes out_counts[q] = min(top_n, candidates) pairs (0 for an id out of range) to out_ids / out_scores[q * top_n ...] */
+int kamd_cong_topk(kamd_engine_h h, int kind, const uint32_t* ids, const uint32_t* bg_ids, const float* weights, uint32_t n, uint32_t top_n,
+                   uint32_t* out_ids, float* out_scores, uint32_t* out_counts);
+/* kind 0 / 1: cosine similarity of n pairs of words / contexts (NaN for an id out of range) */
+int kamd_cong_pairs(kamd_engine_h h, int kind, const uint32_t* a, const uint32_t* b, uint32_t n, float* out);
+int kamd_cong_to_context_id(kamd_engine_h h, const uint32_t* ids, uint32_t n, uint32_t* out_context);
+/* the morpheme sequences of a context (0xFFFFFFFF between two); returns the full length, copies at most max_size */
+int64_t kamd_cong_from_context_id(kamd_engine_h h, uint32_t context_id, uint32_t* out, uint64_t max_size);
+/* test hooks: the 1 / |row| every cosine uses (vocab or contexts floats), and the s8 table itself (rows of dim + 8 bytes; returns its size) */
+int kamd_cong_inv_norms(kamd_engine_h h, int contexts, float* out);
+int64_t kamd_cong_table(kamd_engine_h h, int contexts, uint8_t* out, uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,31 @@ int kiwi_typo_set_lengthening_typo_cost(kiwi_typo_h handle, float threshold);   
 int kiwi_typo_close(kiwi_typo_h handle);                                                         /* capi.h:570 */
 kiwi_prepared_typo_h kiwi_typo_prepare(kiwi_typo_h handle);                                      /* capi.h:580 */
 int kiwi_prepared_typo_close(kiwi_prepared_typo_h handle);                                       /* capi.h:588 */
+/* CoNgram embedding queries (capi.h:1006-1097): answered from the engine's device copies of the CoNgram tables; KIWIERR_FAIL + kiwi_error() (NaN from the two
+ * similarity functions, 0 from kiwi_cong_to_context_id) for a handle whose model is not a CoNgram one.  Ids are the language model's ids.  Differences a caller
+ * can observe:
+ *   - results are ordered by score descending, then id ascending (the reference's order among equal scores comes from partial_sort_copy and is unspecified);
+ *     a NaN score (the cosine of a row whose norm is 0) comes after every number;
+ *   - cosine scores use the correctly rounded 1 / sqrt of each row's norm where the reference uses _mm_rsqrt_ps (an approximation whose bits differ between
+ *     CPU vendors): they differ from the reference's by at most about 2 * 1.5 * 2^-12 relative.  Prediction scores are the reference's bit for bit;
+ *   - a negative top_n / max_size is refused with KIWIERR_FAIL (the reference converts it to size_t and writes as many pairs as the vocabulary has). */
+typedef struct {
+	uint32_t id;
+	float score;
+} kiwi_similarity_pair_t;
+/* top_n pairs at most, min(top_n, vocabulary size) of them; 0 for an id out of range.  The word itself scores -99999. */
+int kiwi_cong_most_similar_words(kiwi_h handle, unsigned int morph_id, kiwi_similarity_pair_t* output, int top_n);                                    /* capi.h:1021 */
+float kiwi_cong_similarity(kiwi_h handle, unsigned int morph_id1, unsigned int morph_id2);                                                              /* capi.h:1031 */
+/* as the reference does, only contexts [0, vocabulary size) are candidates and the count is capped by the vocabulary size; where the model has fewer
+ * contexts than words, contexts [0, context count) (the reference reads past its score buffer there) */
+int kiwi_cong_most_similar_contexts(kiwi_h handle, unsigned int context_id, kiwi_similarity_pair_t* output, int top_n);                               /* capi.h:1042 */
+float kiwi_cong_context_similarity(kiwi_h handle, unsigned int context_id1, unsigned int context_id2);                                                  /* capi.h:1052 */
+int kiwi_cong_predict_words_from_context(kiwi_h handle, unsigned int context_id, kiwi_similarity_pair_t* output, int top_n);                          /* capi.h:1063 */
+int kiwi_cong_predict_words_from_context_diff(kiwi_h handle, unsigned int context_id, unsigned int bg_context_id, float weight, kiwi_similarity_pair_t* output, int top_n); /* capi.h:1076 */
+/* size <= 0 returns 0 (the reference returns an uninitialised value for size 0) */
+unsigned int kiwi_cong_to_context_id(kiwi_h handle, const unsigned int* morph_ids, int size);                                                          /* capi.h:1086 */
+/* the sequences of one context are separated by 0xFFFFFFFF and ordered by length, then lexicographically (the reference's order is its hash map's) */
+int kiwi_cong_from_context_id(kiwi_h handle, unsigned int context_id, unsigned int* morph_ids, int max_size);                                           /* capi.h:1097 */
 
 #ifdef __cplusplus
 }

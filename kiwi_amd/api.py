@@ -374,6 +374,108 @@ class KiwiAmd:
             raise self._err("kamd_fetch")
         return Results(self.lib, r)
 
+    # ---- CoNgram embedding queries (kamd_cong_*; the batched forms of the reference's kiwi_cong_* API)
+    CONG_SIMILAR_WORDS, CONG_SIMILAR_CONTEXTS, CONG_PREDICT, CONG_PREDICT_DIFF = 0, 1, 2, 3
+
+    def _cong_sig(self):
+        L = self.lib
+        if getattr(L, "_cong_sig_done", False):
+            return L
+        P = C.c_void_p
+        L.kamd_cong_info.argtypes = [P, P, P, P]
+        L.kamd_cong_topk.argtypes = [P, C.c_int, P, P, P, C.c_uint32, C.c_uint32, P, P, P]
+        L.kamd_cong_pairs.argtypes = [P, C.c_int, P, P, C.c_uint32, P]
+        L.kamd_cong_to_context_id.argtypes = [P, P, C.c_uint32, P]
+        L.kamd_cong_from_context_id.restype = C.c_int64
+        L.kamd_cong_from_context_id.argtypes = [P, C.c_uint32, P, C.c_uint64]
+        L.kamd_cong_inv_norms.argtypes = [P, C.c_int, P]
+        L.kamd_cong_table.restype = C.c_int64
+        L.kamd_cong_table.argtypes = [P, C.c_int, P, C.c_uint64]
+        L._cong_sig_done = True
+        return L
+
+    def cong_info(self):
+        """(vocabulary size, context count, embedding dim) of the CoNgram model."""
+        out = np.zeros(3, np.uint32)
+        if self._cong_sig().kamd_cong_info(self.h, out[0:].ctypes.data, out[1:].ctypes.data, out[2:].ctypes.data) < 0:
+            raise self._err("kamd_cong_info")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def cong_topk(self, kind, ids, top_n, bg_ids=None, weights=None):
+        """Top-N of every query: (ids [n, top_n] uint32, scores [n, top_n] float32, counts [n] uint32); row q is valid up to counts[q]."""
+        ids = np.ascontiguousarray(ids, np.uint32)
+        n = len(ids)
+        bg = np.ascontiguousarray(bg_ids if bg_ids is not None else np.zeros(n), np.uint32)
+        w = np.ascontiguousarray(weights if weights is not None else np.zeros(n), np.float32)
+        out_ids = np.zeros((n, top_n), np.uint32)
+        out_sc = np.zeros((n, top_n), np.float32)
+        counts = np.zeros(n, np.uint32)
+        if self._cong_sig().kamd_cong_topk(self.h, kind, ids.ctypes.data, bg.ctypes.data, w.ctypes.data, n, top_n,
+                                           out_ids.ctypes.data, out_sc.ctypes.data, counts.ctypes.data) < 0:
+            raise self._err("kamd_cong_topk")
+        return out_ids, out_sc, counts
+
+    def cong_similar_words(self, ids, top_n=10):
+        return self.cong_topk(self.CONG_SIMILAR_WORDS, ids, top_n)
+
+    def cong_similar_contexts(self, ids, top_n=10):
+        return self.cong_topk(self.CONG_SIMILAR_CONTEXTS, ids, top_n)
+
+    def cong_predict(self, context_ids, top_n=10):
+        return self.cong_topk(self.CONG_PREDICT, context_ids, top_n)
+
+    def cong_predict_diff(self, context_ids, bg_ids, weights, top_n=10):
+        return self.cong_topk(self.CONG_PREDICT_DIFF, context_ids, top_n, bg_ids, weights)
+
+    def cong_pairs(self, kind, a, b):
+        """Cosine similarity of pairs of words (kind 0) or contexts (kind 1); NaN for an id out of range."""
+        a = np.ascontiguousarray(a, np.uint32)
+        b = np.ascontiguousarray(b, np.uint32)
+        out = np.zeros(len(a), np.float32)
+        if self._cong_sig().kamd_cong_pairs(self.h, kind, a.ctypes.data, b.ctypes.data, len(a), out.ctypes.data) < 0:
+            raise self._err("kamd_cong_pairs")
+        return out
+
+    def cong_to_context_id(self, ids):
+        ids = np.ascontiguousarray(ids, np.uint32)
+        out = np.zeros(1, np.uint32)
+        if self._cong_sig().kamd_cong_to_context_id(self.h, ids.ctypes.data, len(ids), out.ctypes.data) < 0:
+            raise self._err("kamd_cong_to_context_id")
+        return int(out[0])
+
+    def cong_from_context_id(self, context_id):
+        """The morpheme sequences of a context as a list of uint32 arrays."""
+        L = self._cong_sig()
+        n = L.kamd_cong_from_context_id(self.h, context_id, None, 0)
+        if n < 0:
+            raise self._err("kamd_cong_from_context_id")
+        buf = np.zeros(n, np.uint32)
+        L.kamd_cong_from_context_id(self.h, context_id, buf.ctypes.data, n)
+        if not n:
+            return []
+        return [s[s != 0xFFFFFFFF] for s in np.split(buf, np.flatnonzero(buf == 0xFFFFFFFF))]
+
+    def cong_inv_norms(self, contexts=False):
+        v, c, _ = self.cong_info()
+        out = np.zeros(c if contexts else v, np.float32)
+        if self._cong_sig().kamd_cong_inv_norms(self.h, int(contexts), out.ctypes.data) < 0:
+            raise self._err("kamd_cong_inv_norms")
+        return out
+
+    def cong_table(self, contexts=False):
+        """The s8 table as (rows int8 [n, dim], scale float32 [n], bias float32 [n]; output rows: bias 0)."""
+        L = self._cong_sig()
+        n = L.kamd_cong_table(self.h, int(contexts), None, 0)
+        if n < 0:
+            raise self._err("kamd_cong_table")
+        raw = np.zeros(n, np.uint8)
+        L.kamd_cong_table(self.h, int(contexts), raw.ctypes.data, n)
+        dim = self.cong_info()[2]
+        rows = raw.reshape(-1, dim + 8)
+        emb = rows[:, :dim].view(np.int8)
+        tail = np.ascontiguousarray(rows[:, dim:]).view(np.float32)
+        return emb, tail[:, 0].copy(), (tail[:, 1].copy() if contexts else np.zeros(len(rows), np.float32))
+
     def dump_dict(self) -> bytes:
         buf = np.zeros(1 << 20, np.uint8)
         while True:

@@ -20,6 +20,8 @@
 #include "engine.hpp"
 #include "hostpool.hpp"
 #include "typo.hpp"
+#include "cong_query_kernel.hpp"
+#include <cmath>
 
 using namespace kamd;
 
@@ -762,5 +764,70 @@ extern "C"
 		}
 		else delete r;
 		return 0;
+	}
+	// ---- CoNgram embedding queries (capi.h:1006-1097; src/capi/kiwi_c.cpp:1404-1550) on the handle's engine (Engine::congQuery ...)
+	static int congTopN(kiwi_h h, uint32_t kind, uint32_t id, uint32_t bg, float weight, kiwi_similarity_pair_t* output, int top_n)
+	{
+		if (!h) return KIWIERR_INVALID_HANDLE;
+		try
+		{
+			if (!h->engine->hasCongTables()) throw std::invalid_argument{ "The given kiwi object does not have CoNgram language model." };
+			if (top_n < 0) throw std::invalid_argument{ "top_n must not be negative" };
+			if (top_n && !output) throw std::invalid_argument{ "output is null" };
+			std::vector<uint32_t> ids((size_t)top_n); std::vector<float> scores((size_t)top_n);
+			uint32_t cnt = 0;
+			h->engine->congQuery(kind, &id, &bg, &weight, 1, (size_t)top_n, ids.data(), scores.data(), &cnt);
+			for (uint32_t i = 0; i < cnt; ++i) { output[i].id = ids[i]; output[i].score = scores[i]; }
+			return (int)cnt;
+		}
+		catch (const std::exception& e) { setError(e); return KIWIERR_FAIL; }
+	}
+	static float congPair(kiwi_h h, uint32_t kind, uint32_t a, uint32_t b)
+	{
+		if (!h) return NAN;
+		try
+		{
+			if (!h->engine->hasCongTables()) throw std::invalid_argument{ "The given kiwi object does not have CoNgram language model." };
+			float r = NAN;
+			h->engine->congPairs(kind, &a, &b, 1, &r);
+			return r;
+		}
+		catch (const std::exception& e) { setError(e); return NAN; }
+	}
+	int kiwi_cong_most_similar_words(kiwi_h h, unsigned int morph_id, kiwi_similarity_pair_t* output, int top_n) { return congTopN(h, CQ_SIMILAR_WORDS, morph_id, 0, 0.f, output, top_n); }
+	float kiwi_cong_similarity(kiwi_h h, unsigned int morph_id1, unsigned int morph_id2) { return congPair(h, CQ_SIMILAR_WORDS, morph_id1, morph_id2); }
+	int kiwi_cong_most_similar_contexts(kiwi_h h, unsigned int context_id, kiwi_similarity_pair_t* output, int top_n) { return congTopN(h, CQ_SIMILAR_CONTEXTS, context_id, 0, 0.f, output, top_n); }
+	float kiwi_cong_context_similarity(kiwi_h h, unsigned int context_id1, unsigned int context_id2) { return congPair(h, CQ_SIMILAR_CONTEXTS, context_id1, context_id2); }
+	int kiwi_cong_predict_words_from_context(kiwi_h h, unsigned int context_id, kiwi_similarity_pair_t* output, int top_n) { return congTopN(h, CQ_PREDICT, context_id, 0, 0.f, output, top_n); }
+	int kiwi_cong_predict_words_from_context_diff(kiwi_h h, unsigned int context_id, unsigned int bg_context_id, float weight, kiwi_similarity_pair_t* output, int top_n)
+	{
+		return congTopN(h, CQ_PREDICT_DIFF, context_id, bg_context_id, weight, output, top_n);
+	}
+	unsigned int kiwi_cong_to_context_id(kiwi_h h, const unsigned int* morph_ids, int size)
+	{
+		if (!h) return 0;
+		try
+		{
+			if (!h->engine->hasCongTables()) throw std::invalid_argument{ "The given kiwi object does not have CoNgram language model." };
+			if (size <= 0) return 0;
+			return h->engine->congToContextId(morph_ids, (size_t)size);
+		}
+		catch (const std::exception& e) { setError(e); return 0; }
+	}
+	int kiwi_cong_from_context_id(kiwi_h h, unsigned int context_id, unsigned int* morph_ids, int max_size)
+	{
+		if (!h) return KIWIERR_INVALID_HANDLE;
+		try
+		{
+			if (!h->engine->hasCongTables()) throw std::invalid_argument{ "The given kiwi object does not have CoNgram language model." };
+			if (max_size < 0) throw std::invalid_argument{ "max_size must not be negative" };
+			const auto& map = h->engine->congContextWordMap();
+			if ((size_t)context_id >= map.size()) throw std::out_of_range{ "Invalid context ID." };
+			const auto& v = map[context_id];
+			const int n = (int)std::min<size_t>(v.size(), (size_t)max_size);
+			for (int i = 0; i < n; ++i) morph_ids[i] = v[i];
+			return n;
+		}
+		catch (const std::exception& e) { setError(e); return KIWIERR_FAIL; }
 	}
 }

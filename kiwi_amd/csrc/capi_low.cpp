@@ -479,4 +479,59 @@ extern "C"
 		if (!h) return 0;
 		return guarded([&]() { auto d = h->e->dumpLattices((const char16_t*)text, len, match); if (d.size() <= cap) std::memcpy(out, d.data(), d.size()); return d.size(); }, (size_t)0);
 	}
+	// ---- CoNgram embedding queries (kiwi_amd.h; Engine::congQuery ...)
+	int kamd_cong_info(kamd_engine_h h, uint32_t* vocab, uint32_t* contexts, uint32_t* dim)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]() { uint32_t v, c, d; h->e->congInfo(v, c, d); if (vocab) *vocab = v; if (contexts) *contexts = c; if (dim) *dim = d; return 0; }, -1);
+	}
+	int kamd_cong_topk(kamd_engine_h h, int kind, const uint32_t* ids, const uint32_t* bg_ids, const float* weights, uint32_t n, uint32_t top_n,
+		uint32_t* out_ids, float* out_scores, uint32_t* out_counts)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]()
+		{
+			if (kind < 0 || kind > 3) throw std::invalid_argument{ "kamd_cong_topk: kind must be 0 .. 3" };
+			h->e->congQuery((uint32_t)kind, ids, bg_ids, weights, n, top_n, out_ids, out_scores, out_counts);
+			return 0;
+		}, -1);
+	}
+	int kamd_cong_pairs(kamd_engine_h h, int kind, const uint32_t* a, const uint32_t* b, uint32_t n, float* out)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]() { if (kind != 0 && kind != 1) throw std::invalid_argument{ "kamd_cong_pairs: kind must be 0 or 1" }; h->e->congPairs((uint32_t)kind, a, b, n, out); return 0; }, -1);
+	}
+	int kamd_cong_to_context_id(kamd_engine_h h, const uint32_t* ids, uint32_t n, uint32_t* out_context)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]() { *out_context = h->e->congToContextId(ids, n); return 0; }, -1);
+	}
+	int64_t kamd_cong_from_context_id(kamd_engine_h h, uint32_t context_id, uint32_t* out, uint64_t max_size)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]()
+		{
+			const auto& map = h->e->congContextWordMap();
+			if (context_id >= map.size()) throw std::out_of_range{ "Invalid context ID." };
+			const auto& v = map[context_id];
+			for (size_t i = 0; i < v.size() && i < max_size; ++i) out[i] = v[i];
+			return (int64_t)v.size();
+		}, (int64_t)-1);
+	}
+	int kamd_cong_inv_norms(kamd_engine_h h, int contexts, float* out)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]() { const auto& v = h->e->congInvNorms(contexts != 0); std::copy(v.begin(), v.end(), out); return 0; }, -1);
+	}
+	int64_t kamd_cong_table(kamd_engine_h h, int contexts, uint8_t* out, uint64_t cap)
+	{
+		if (!h) { lastError = "null engine"; return -1; }
+		return guarded([&]()
+		{
+			if (!h->e->hasCongTables()) throw std::runtime_error{ "The given engine does not have CoNgram language model." };
+			const auto& t = contexts ? h->e->model().congCtxEmb : h->e->model().congOutEmb;
+			if (out) std::memcpy(out, t.data(), std::min<size_t>(t.size(), cap));
+			return (int64_t)t.size();
+		}, (int64_t)-1);
+	}
 }

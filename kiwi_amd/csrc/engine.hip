@@ -26,6 +26,7 @@
 #include "chr_freq.hpp"
 #include "typo_lattice_kernel.hpp"
 #include "typo_graph_kernel.hpp"
+#include "cong_query_kernel.hpp"
 
 namespace kamd
 {
@@ -299,6 +300,13 @@ namespace kamd
 		// is callable from many threads, reference capi threading contract) is serialised per engine; host preparation is not
 		std::recursive_mutex deviceMu;
 		TokenTemplates tokTmpl;      // (post_fast.hpp; built with the first fetch)
+		// the CoNgram query API (Engine::congQuery ...): a stream, scratch and lock of its own, so that queries run beside analyses; the row norms and the
+		// context -> morphemes map are made on first use
+		std::mutex congMu; hipStream_t congStream = nullptr; bool congNormsOnDevice = false;
+		DevBuf congIds, congBg, congW, congScores, congOutIds, congOutScores, congInvOut, congInvCtx;
+		std::once_flag congNormOnce, congMapOnce;
+		std::vector<float> congNormOut, congNormCtx;
+		std::vector<std::vector<uint32_t>> congWordMap;
 
 		// room behind the model's form / morpheme tables for the temporary entries of a batch with pretokenized spans (TempOverlay): elements per table
 		static constexpr size_t kTempForms = 4096, kTempMorphs = 8192, kTempChars = 1u << 17, kTempCand = 16384, kTempChunks = 16384;
@@ -484,9 +492,11 @@ namespace kamd
 			// the engine's own blocks go back to the cache first, then the cache is emptied: nothing stays allocated after the last engine
 			impl->modelBufs.clear();
 			impl->bigScratch.release(); impl->posScratch.release(); impl->counter.release(); impl->sbgScratch.release();
+			for (DevBuf* d : { &impl->congIds, &impl->congBg, &impl->congW, &impl->congScores, &impl->congOutIds, &impl->congOutScores, &impl->congInvOut, &impl->congInvCtx }) d->release();
 			devCache().trim();
 			if (impl->stream) (void)hipStreamDestroy(impl->stream);
 			if (impl->stream2) (void)hipStreamDestroy(impl->stream2);
+			if (impl->congStream) (void)hipStreamDestroy(impl->congStream);
 			for (auto ls : impl->latStream) if (ls) (void)hipStreamDestroy(ls);
 			if (impl->streamCopy) (void)hipStreamDestroy(impl->streamCopy);
 			if (impl->lastDone) (void)hipEventDestroy(impl->lastDone);
@@ -2376,5 +2386,308 @@ namespace kamd
 			}
 		}
 		return out;
+	}
+	// ---- CoNgram query API (engine.hpp; the reference's CoNgramModel::mostSimilarWords ... getContextWordMap, src/CoNgramModel.cpp:2416-2870)
+#ifdef KAMD_HIPEMU
+	// the lane emulator (KAMD_HIPEMU builds, test infrastructure) compiles the analyze path's sources only: no query kernels there
+	void launchCongScores(const CongQueryTables&, uint32_t, const uint32_t*, const uint32_t*, const float*, uint32_t, uint32_t, float*, hipStream_t)
+	{
+		throw std::runtime_error{ "the CoNgram query kernels are not part of the lane emulator" };
+	}
+	void launchCongTopN(const float*, uint32_t, uint32_t, uint32_t, uint32_t*, float*, hipStream_t)
+	{
+		throw std::runtime_error{ "the CoNgram query kernels are not part of the lane emulator" };
+	}
+#endif
+	namespace
+	{
+		const char* const kNoCong = "The given kiwi object does not have CoNgram language model.";      // (src/capi/kiwi_c.cpp:1411)
+		struct CongRow { const int8_t* v; float scale, bias; };
+		CongRow congRow(const std::vector<uint8_t>& table, uint32_t dim, uint32_t r)
+		{
+			const uint8_t* p = table.data() + (size_t)r * (dim + 8);
+			CongRow row{ reinterpret_cast<const int8_t*>(p), 0.f, 0.f };
+			std::memcpy(&row.scale, p + dim, 4); std::memcpy(&row.bias, p + dim + 4, 4);
+			return row;
+		}
+		int32_t congDot(const int8_t* a, const int8_t* b, uint32_t dim)
+		{
+			int32_t acc = 0;
+			for (uint32_t k = 0; k < dim; ++k) acc += (int32_t)a[k] * (int32_t)b[k];
+			return acc;
+		}
+	}
+
+	bool Engine::hasCongTables() const { return impl->hasCong; }
+	void Engine::congInfo(uint32_t& vocab, uint32_t& contexts, uint32_t& dim) const
+	{
+		if (!impl->hasCong) throw std::runtime_error{ kNoCong };
+		vocab = impl->model.congVocab; contexts = impl->model.congCtx; dim = impl->model.congDim;
+	}
+
+	const std::vector<float>& Engine::congInvNorms(bool contexts)
+	{
+		if (!impl->hasCong) throw std::runtime_error{ kNoCong };
+		std::call_once(impl->congNormOnce, [this]()
+		{
+			const FlatModel& m = impl->model;
+			const auto norms = [&](const std::vector<uint8_t>& table, uint32_t rows, std::vector<float>& out)
+			{
+				out.resize(rows);
+				for (uint32_t r = 0; r < rows; ++r) { const CongRow row = congRow(table, m.congDim, r); out[r] = congInvNorm(congDot(row.v, row.v, m.congDim), row.scale); }
+			};
+			norms(m.congOutEmb, m.congVocab, impl->congNormOut);
+			norms(m.congCtxEmb, m.congCtx, impl->congNormCtx);
+		});
+		return contexts ? impl->congNormCtx : impl->congNormOut;
+	}
+
+	void Engine::congPairs(uint32_t kind, const uint32_t* a, const uint32_t* b, size_t n, float* out)
+	{
+		if (kind != CQ_SIMILAR_WORDS && kind != CQ_SIMILAR_CONTEXTS) throw std::invalid_argument{ "congPairs: kind must be 0 (words) or 1 (contexts)" };
+		const bool ctx = kind == CQ_SIMILAR_CONTEXTS;
+		const std::vector<float>& inv = congInvNorms(ctx);
+		const FlatModel& m = impl->model;
+		const std::vector<uint8_t>& table = ctx ? m.congCtxEmb : m.congOutEmb;
+		const uint32_t rows = ctx ? m.congCtx : m.congVocab;
+		for (size_t i = 0; i < n; ++i)
+		{
+			if (a[i] >= rows || b[i] >= rows) { out[i] = NAN; continue; }
+			const CongRow x = congRow(table, m.congDim, a[i]), y = congRow(table, m.congDim, b[i]);
+			out[i] = congCosine(congDot(x.v, y.v, m.congDim), x.scale, y.scale, inv[a[i]], inv[b[i]]);
+		}
+	}
+
+	void Engine::congQuery(uint32_t kind, const uint32_t* ids, const uint32_t* bg, const float* weights, size_t n, size_t topN,
+		uint32_t* outIds, float* outScores, uint32_t* counts)
+	{
+		if (!impl->hasCong) throw std::runtime_error{ kNoCong };
+		if (kind > CQ_PREDICT_DIFF) throw std::invalid_argument{ "congQuery: kind must be 0 .. 3" };
+		if (impl->model.congDim > 64) throw std::runtime_error{ "congQuery: embedding dims above 64 are not supported" };      // (the kernel stages a query row of <= 64 + 8 bytes)
+		if (kind == CQ_PREDICT_DIFF && (!bg || !weights)) throw std::invalid_argument{ "congQuery: the diff kind needs background ids and weights" };
+		const FlatModel& m = impl->model;
+		const uint32_t V = m.congVocab, C = m.congCtx;
+		// candidates: the vocabulary; for similar contexts the reference iterates i < vocabSize over the context scores (:2535-2541) -- contexts [0, V),
+		// restricted here to [0, C) where C < V (the reference reads past its buffer there)
+		const uint32_t nCand = kind == CQ_SIMILAR_CONTEXTS ? std::min(V, C) : V;
+		const uint32_t idRange = kind == CQ_SIMILAR_WORDS ? V : C;
+		const uint32_t cnt = (uint32_t)std::min<size_t>(topN, nCand);
+		std::vector<uint32_t> valid;
+		for (size_t q = 0; q < n; ++q)
+		{
+			const bool ok = ids[q] < idRange && (kind != CQ_PREDICT_DIFF || bg[q] < C);
+			counts[q] = ok ? cnt : 0;
+			if (ok && cnt) valid.push_back((uint32_t)q);
+		}
+		if (valid.empty()) return;
+		congInvNorms(false);      // (both tables' norms, whatever the kind: the device copies below are made once, by the first query of any kind)
+		Impl& I = *impl;
+		std::lock_guard<std::mutex> g{ I.congMu };
+		bindThread();
+		if (!I.congStream) HIPCHECK(hipStreamCreateWithFlags(&I.congStream, hipStreamNonBlocking));
+		if (!I.congNormsOnDevice)
+		{
+			I.congInvOut.ensure(std::max<size_t>(V, 1) * 4); I.congInvCtx.ensure(std::max<size_t>(C, 1) * 4);
+			HIPCHECK(hipMemcpyAsync(I.congInvOut.p, I.congNormOut.data(), (size_t)V * 4, hipMemcpyHostToDevice, I.congStream));
+			HIPCHECK(hipMemcpyAsync(I.congInvCtx.p, I.congNormCtx.data(), (size_t)C * 4, hipMemcpyHostToDevice, I.congStream));
+			I.congNormsOnDevice = true;      // (set after both copies were enqueued: a failed upload is tried again by the next query)
+		}
+		hipStream_t st = I.congStream;
+		const CongQueryTables T{ I.cong.ctxEmb, I.cong.outEmb, I.congInvOut.as<float>(), I.congInvCtx.as<float>(), m.congDim, m.congDim + 8 };
+		const bool fused = cnt <= kCongFusedTopN;
+		// queries per launch: the score rows of a chunk take at most 64 MB
+		const size_t chunk = std::max<size_t>(1, std::min<size_t>(65535, (size_t(16) << 20) / nCand));
+		const size_t cq = std::min(chunk, valid.size());
+		I.congIds.ensure(cq * 4); I.congBg.ensure(cq * 4); I.congW.ensure(cq * 4); I.congScores.ensure(cq * nCand * 4);
+		if (fused) { I.congOutIds.ensure(cq * cnt * 4); I.congOutScores.ensure(cq * cnt * 4); }
+		std::vector<uint32_t> hIds(cq), hBg(cq), hSel; std::vector<float> hW(cq), hSc;
+		for (size_t c0 = 0; c0 < valid.size(); c0 += chunk)
+		{
+			const uint32_t nq = (uint32_t)std::min(chunk, valid.size() - c0);
+			for (uint32_t j = 0; j < nq; ++j)
+			{
+				const uint32_t q = valid[c0 + j];
+				hIds[j] = ids[q]; hBg[j] = kind == CQ_PREDICT_DIFF ? bg[q] : 0u; hW[j] = kind == CQ_PREDICT_DIFF ? weights[q] : 0.f;
+			}
+			HIPCHECK(hipMemcpyAsync(I.congIds.p, hIds.data(), nq * 4, hipMemcpyHostToDevice, st));
+			HIPCHECK(hipMemcpyAsync(I.congBg.p, hBg.data(), nq * 4, hipMemcpyHostToDevice, st));
+			HIPCHECK(hipMemcpyAsync(I.congW.p, hW.data(), nq * 4, hipMemcpyHostToDevice, st));
+			launchCongScores(T, kind, I.congIds.as<uint32_t>(), I.congBg.as<uint32_t>(), I.congW.as<float>(), nq, nCand, I.congScores.as<float>(), st);
+			HIPCHECK(hipGetLastError());
+			if (fused)
+			{
+				launchCongTopN(I.congScores.as<float>(), nq, nCand, cnt, I.congOutIds.as<uint32_t>(), I.congOutScores.as<float>(), st);
+				HIPCHECK(hipGetLastError());
+				hSel.resize((size_t)nq * cnt); hSc.resize((size_t)nq * cnt);
+				HIPCHECK(hipMemcpyAsync(hSel.data(), I.congOutIds.p, hSel.size() * 4, hipMemcpyDeviceToHost, st));
+				HIPCHECK(hipMemcpyAsync(hSc.data(), I.congOutScores.p, hSc.size() * 4, hipMemcpyDeviceToHost, st));
+				HIPCHECK(hipStreamSynchronize(st));
+				for (uint32_t j = 0; j < nq; ++j)
+				{
+					const size_t q = valid[c0 + j];
+					std::memcpy(outIds + q * topN, hSel.data() + (size_t)j * cnt, cnt * 4);
+					std::memcpy(outScores + q * topN, hSc.data() + (size_t)j * cnt, cnt * 4);
+				}
+			}
+			else
+			{
+				// N beyond the selection kernel: every score comes back and is ordered here, with the same key
+				hSc.resize((size_t)nq * nCand);
+				HIPCHECK(hipMemcpyAsync(hSc.data(), I.congScores.p, hSc.size() * 4, hipMemcpyDeviceToHost, st));
+				HIPCHECK(hipStreamSynchronize(st));
+				std::vector<uint64_t> keys(nCand);
+				for (uint32_t j = 0; j < nq; ++j)
+				{
+					const float* row = hSc.data() + (size_t)j * nCand;
+					for (uint32_t i = 0; i < nCand; ++i) keys[i] = (uint64_t)congOrderKey(row[i]) << 32 | i;
+					std::partial_sort(keys.begin(), keys.begin() + cnt, keys.end());
+					const size_t q = valid[c0 + j];
+					for (uint32_t r = 0; r < cnt; ++r) { const uint32_t i = (uint32_t)keys[r]; outIds[q * topN + r] = i; outScores[q * topN + r] = row[i]; }
+				}
+			}
+		}
+	}
+
+	namespace
+	{
+		// an edge of node n (binary search of its sorted keys); false where the key is absent or its value is 0
+		bool congHostSearch(const FlatModel& m, const CongNodeRec& n, uint32_t key, int32_t& v)
+		{
+			const uint32_t* k = m.congKeys.data() + n.nextOff;
+			const uint32_t* it = std::lower_bound(k, k + n.numNexts, key);
+			if (it == k + n.numNexts || *it != key) return false;
+			v = m.congValues[n.nextOff + (it - k)];
+			return v != 0;
+		}
+		// progressContextNodeVl (src/CoNgramModel.hpp:306-385) over the host trie: the context id `key` leads to from `node`
+		uint32_t congHostStep(const FlatModel& m, int32_t& node, uint32_t key)
+		{
+			const auto rootValue = [&](uint32_t k) { return k < m.congRoot.size() ? m.congRoot[k] : 0; };
+			for (;;)
+			{
+				int32_t v = 0;
+				if (node != 0)
+				{
+					const CongNodeRec& nd = m.congNodes[node];
+					if (!congHostSearch(m, nd, key, v)) { if (!nd.lower) return 0; node += nd.lower; continue; }
+				}
+				else if ((v = rootValue(key)) == 0) return 0;
+				if (v > 0) { node += v; return m.congNodes[node].value; }
+				int32_t nd = node;
+				while (m.congNodes[nd].lower)
+				{
+					nd += m.congNodes[nd].lower;
+					int32_t lv = 0;
+					if (nd != 0) { if (congHostSearch(m, m.congNodes[nd], key, lv) && lv > 0) { node = nd + lv; return (uint32_t)-v; } }
+					else if ((lv = rootValue(key)) > 0) { node = lv; return (uint32_t)-v; }
+				}
+				node = 0;
+				return (uint32_t)-v;
+			}
+		}
+
+		// visitContextNode (src/CoNgramModel.cpp:2758-2830): every (key sequence -> context id) the trie names, by sequence length; the first
+		// sequence a decoded form takes is kept
+		void congVisit(const FlatModel& m, int32_t node, std::vector<uint32_t>& prefix, std::vector<std::map<std::vector<uint32_t>, uint32_t>>& out)
+		{
+			const auto insert = [&](uint32_t ctx)
+			{
+				std::vector<uint32_t> buf;
+				if (m.congVlTMax == 0xFFFFFFFFu) buf = prefix;
+				else
+				{
+					// the reference's two-key decode (tMax = 65536 - 2048; high << 10 | low, without adding tMax back)
+					const uint64_t tMax = m.congVlTMax;
+					for (size_t j = 0; j < prefix.size(); ++j)
+					{
+						if (j + 1 < prefix.size() && prefix[j] >= tMax && prefix[j + 1] >= tMax)
+						{
+							const uint64_t high = prefix[j] - tMax, low = (uint64_t)prefix[j + 1] - tMax - (1u << m.congVlBits);
+							buf.push_back((uint32_t)((high << m.congVlBits) | low));
+							++j;
+						}
+						else buf.push_back(prefix[j]);
+					}
+				}
+				if (out.size() < buf.size()) out.resize(buf.size());
+				out[buf.size() - 1].emplace(std::move(buf), ctx);
+			};
+			const CongNodeRec nd = m.congNodes[node];
+			for (uint32_t i = 0; i < nd.numNexts; ++i)
+			{
+				uint32_t k; int32_t v;
+				if (node == 0) { k = i; v = i < m.congRoot.size() ? m.congRoot[i] : 0; }      // (the reference walks keys 0 .. numNexts - 1 of its root table)
+				else { k = m.congKeys[nd.nextOff + i]; v = m.congValues[nd.nextOff + i]; }
+				prefix.push_back(k);
+				if (v > 0)
+				{
+					if (const uint32_t value = m.congNodes[node + v].value) insert(value);
+					congVisit(m, node + v, prefix, out);
+				}
+				else if (v < 0) insert((uint32_t)-v);
+				prefix.pop_back();
+			}
+		}
+	}
+
+	uint32_t Engine::congToContextId(const uint32_t* ids, size_t n) const
+	{
+		if (!impl->hasCong) throw std::runtime_error{ kNoCong };
+		const FlatModel& m = impl->model;
+		int32_t node = 0;
+		uint32_t ctx = 0;
+		for (size_t i = 0; i < n; ++i)
+		{
+			// progressContextNode (src/CoNgramModel.hpp:271-300): 16-bit keys take the id's low half; variable-length keys spell a large id as two keys
+			const uint32_t next = m.congKeyBytes == 2 ? (ids[i] & 0xFFFFu) : ids[i];
+			if (next < m.congVlTMax) ctx = congHostStep(m, node, next);
+			else
+			{
+				const uint32_t r = next - m.congVlTMax;
+				congHostStep(m, node, m.congVlTMax + (r >> m.congVlBits));
+				ctx = congHostStep(m, node, m.congVlTMax + (1u << m.congVlBits) + (r & ((1u << m.congVlBits) - 1)));
+			}
+		}
+		return ctx;
+	}
+
+	const std::vector<std::vector<uint32_t>>& Engine::congContextWordMap()
+	{
+		if (!impl->hasCong) throw std::runtime_error{ kNoCong };
+		std::call_once(impl->congMapOnce, [this]()
+		{
+			const FlatModel& m = impl->model;
+			std::vector<std::map<std::vector<uint32_t>, uint32_t>> byLen;
+			std::vector<uint32_t> prefix;
+			congVisit(m, 0, prefix, byLen);
+			// redundant sequences (src/CoNgramModel.cpp:2838-2861): a sequence goes when its longest shorter suffix that is itself a sequence names the same context
+			for (size_t i = byLen.size(); i-- > 0;)
+			{
+				auto& c = byLen[i];
+				for (auto it = c.begin(); it != c.end();)
+				{
+					bool erase = false;
+					for (size_t j = i; j-- > 0;)
+					{
+						const std::vector<uint32_t> suffix(it->first.end() - (j + 1), it->first.end());
+						const auto found = byLen[j].find(suffix);
+						if (found != byLen[j].end()) { erase = found->second == it->second; break; }
+					}
+					it = erase ? c.erase(it) : std::next(it);
+				}
+			}
+			// by length, then lexicographically (the reference's order is its hash map's)
+			auto& map = impl->congWordMap;
+			map.assign(m.congCtx, {});
+			for (auto& c : byLen)
+				for (auto& p : c)
+				{
+					if (p.second >= m.congCtx) continue;
+					auto& target = map[p.second];
+					if (!target.empty()) target.push_back(0xFFFFFFFFu);
+					target.insert(target.end(), p.first.begin(), p.first.end());
+				}
+		});
+		return impl->congWordMap;
 	}
 }

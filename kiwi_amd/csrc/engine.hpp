@@ -112,6 +112,22 @@ namespace kamd
 		// chunks of the last run() that overflowed their scratch in the first pass and were searched again inside run(), and the wall time of that
 		static uint32_t rerunChunks(const StagedBatch& b, float* ms);
 
+		// ---- queries of the CoNgram model's embedding tables (the reference's kiwi_cong_* API, src/CoNgramModel.cpp:2416-2870).  Own stream, scratch and
+		// mutex: safe beside analyzeBatch on the same engine, and they leave its results unchanged.  Every call throws without a CoNgram model.
+		bool hasCongTables() const;
+		void congInfo(uint32_t& vocab, uint32_t& contexts, uint32_t& dim) const;
+		// kind: cong_query_kernel.hpp CongQueryKind; ids / bg / weights: n queries (bg, weights: CQ_PREDICT_DIFF only).  Query q's results go to
+		// outIds / outScores[q * topN ...], counts[q] of them: min(topN, candidates), 0 for an id out of range
+		void congQuery(uint32_t kind, const uint32_t* ids, const uint32_t* bg, const float* weights, size_t n, size_t topN,
+			uint32_t* outIds, float* outScores, uint32_t* counts);
+		// kind CQ_SIMILAR_WORDS / CQ_SIMILAR_CONTEXTS: cosine of n pairs (NaN for an id out of range), on the host with the kernel's formula
+		void congPairs(uint32_t kind, const uint32_t* a, const uint32_t* b, size_t n, float* out);
+		const std::vector<float>& congInvNorms(bool contexts);
+		// CoNgramModel::toContextId (progressContextNode from node 0 over the ids): 0 for n == 0 or an id outside the trie's root table
+		uint32_t congToContextId(const uint32_t* ids, size_t n) const;
+		// getContextWordMap: the morpheme sequences of every context, 0xFFFFFFFF between two sequences (built once per engine)
+		const std::vector<std::vector<uint32_t>>& congContextWordMap();
+
 		// debugging / parity hooks: lattice of every chunk of one text in the layout of oracle's korc_split
 		std::vector<uint8_t> dumpLattices(const char16_t* text, size_t n, uint64_t match);
 		// ... and the lattices built over the typo graphs a prepared transformer gives for the chunks (typo_lattice_kernel.hip); same layout.

@@ -226,6 +226,38 @@ namespace kamd
 		return (float)acc * cs * os + bias;
 	}
 
+	// ---- the query API over the same tables (kiwi_cong_*; cong_query_kernel.hip, engine.hip): one helper per score formula, shared by the kernel,
+	// the host paths and the tests' restatement.  `dot` is the exact int32 product of the two s8 rows.
+	// cosine of two rows of one table (mostSimilarWords / wordSimilarity / mostSimilarContexts / contextSimilarity, src/CoNgramModel.cpp:2416-2560): the
+	// gemv's (float)dot * scale(query) * scale(candidate), then gemm::mul's c *= invNorm(query) * invNorm(candidate)
+	KAMD_HD float congCosine(int32_t dot, float scaleQ, float scaleI, float invNormQ, float invNormI)
+	{
+		const float s = (float)dot * scaleQ * scaleI;
+		return s * (invNormQ * invNormI);
+	}
+	// predictWordsFromContext (:2598-2632): congScore's arithmetic
+	KAMD_HD float congPredict(int32_t dot, float ctxScale, float outScale, float ctxBias) { return (float)dot * ctxScale * outScale + ctxBias; }
+	// predictWordsFromContextDiff (:2660-2745): both scores without their bias, the biases combined once
+	KAMD_HD float congPredictDiff(int32_t dotC, int32_t dotBg, float scaleC, float scaleBg, float outScale, float biasC, float biasBg, float weight)
+	{
+		const float sc = (float)dotC * scaleC * outScale, sb = (float)dotBg * scaleBg * outScale;
+		const float bias = biasC - biasBg * weight;
+		return (sc - sb * weight) + bias;
+	}
+	// 1 / |row| from the reference's pre-rsqrt value (invNormS8_128 / invNormU8_128, src/archImpl/sse4_1.cpp:328-427).  The reference applies
+	// _mm_rsqrt_ps (a ~12-bit approximation whose bits differ between CPU vendors); this is the correctly rounded 1 / sqrt.
+	KAMD_HD float congInvNorm(int32_t sumsq, float scale) { return 1.0f / sqrtf((float)sumsq * scale * scale); }
+	// order of query results: score descending, then id ascending.  The key of a score: smaller key = better score; -0 and +0 are one score;
+	// NaN (the cosine of a row whose norm is 0) after every number
+	KAMD_HD uint32_t congOrderKey(float s)
+	{
+		if (s != s) return 0xFFFFFFFFu;
+		if (s == 0.0f) s = 0.0f;
+		uint32_t u; __builtin_memcpy(&u, &s, 4);
+		u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);     // ascending in the score
+		return ~u;
+	}
+
 	// the same with the output scale multiplied in first: the rounding of the reference's batched SSE4.1 kernel (src/archImpl/sse4_1.cpp:116)
 	KAMD_HD float congScoreOutputFirst(const CongView& C, uint32_t c, uint32_t w)
 	{
