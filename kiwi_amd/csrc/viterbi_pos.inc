@@ -12,11 +12,12 @@
 //     by the incoming paths.
 // A step (four chunks per wavefront, a 16-lane group each, all four in lock step): a group's lanes 0..m-1 look its m nodes' predecessor state
 // ranges up (LDS ring), lanes 0..nRec-1 turn its records into item counts (paths x start states).  Then the WAVEFRONT packs the items of all four
-// groups into its 64 lanes -- records in lane order, a record never split across a 16-lane row -- and scores them together, one per lane (side terms
-// + LM walk): a position has ~13 items, so four of them fill one wavefront where four separate 16-lane rounds left a quarter of the lanes idle and
-// every group waiting for the slowest group's second round (26 % of a step, profiles/r03_j_pos_phases_c2.txt).  The per-key winner of the
-// reference's path container (BestPathContainer.hpp:279-483; a key never spans two candidates, and carries its record here) comes from segmented
-// scans -- one pass per distinct key of a record, the segments being the records of a row; kept states stream to their group's arena in item order;
+// groups into its 64 lanes -- records in lane order, a round being the next up to 64 items whatever 16-lane rows a record falls in -- and scores them
+// together, one per lane (side terms + LM walk): a position has ~13 items, so four of them fill one wavefront where four separate 16-lane rounds left
+// a quarter of the lanes idle and every group waiting for the slowest group's second round (26 % of a step, profiles/r03_j_pos_phases_c2.txt).  The
+// per-key winner of the reference's path container (BestPathContainer.hpp:279-483; a key never spans two candidates, and carries its record here)
+// comes from segmented scans -- one pass per distinct key of a record, the segments being the records, scanned along the rows and carried across
+// them; kept states stream to their group's arena in item order;
 // back in the groups, pruning per (node, root) against the best socket-free score (PathEvaluator.hpp:475-511) is 15 rotations of the row and lanes
 // 0..m-1 commit the nodes' state ranges.  The reference's fallbacks run inside the step: the retry without left-condition penalties, the second reading
 // of all-partial forms, the z-coda / z-siot shortcut (records of their own), and the disconnected-lattice test as reachability bit sets over positions.
@@ -45,11 +46,9 @@
 #endif
 		static constexpr uint32_t PHR = G == 16 ? 32 : 16;      // most recent states whose hot quad (+ typo cost[, context id]) is kept in LDS: what a following step reads of a state
 	};
-	constexpr uint32_t PBIG_CAP = 64;      // items of one record beyond which the position is handed over (a record of more than 16 gets the wavefront to itself)
-	// a record of more than 16 items: key, score, first-chunk score, context id of its items, staged in HBM (WorkView::posBig, one block per lane group)
-	struct PosBigItem { uint32_t keyLo, keyHi; float score, fcs; uint32_t ctx; };
+	constexpr uint32_t PBIG_CAP = 64;      // items of one record beyond which the position is handed over (a round is one wavefront of items, and a record is never split over two rounds)
 	// what the lanes that score a group's items need of the group (its lane 0 keeps it current in LDS): 16 dwords
-	struct PosGroupCtx { uint64_t st, recs, uniq, nodeTypo; uint32_t stCap, stTop, posStart, ringTop, firstRec, retry, ofNodes, bigBase; };
+	struct PosGroupCtx { uint64_t st, recs, uniq, nodeTypo; uint32_t stCap, stTop, posStart, ringTop, firstRec, retry, ofNodes, pad; };
 	static_assert(sizeof(PosGroupCtx) == 64, "PosGroupCtx");
 	template<int G> struct PosLayT
 	{
@@ -57,7 +56,17 @@
 		static constexpr uint32_t RBEG = 0, REND = 4 * RING, RCUM = 8 * RING;      // as the general kernel's ring: first state / end / running live total of the last RING nodes
 		static constexpr uint32_t NCNT = 12 * RING;                                   // u32[G]: per node of the position -- states | own-candidate states << 8 | live << 16 | live socket-free << 24
 		static constexpr uint32_t ACUR = NCNT + 4 * G, ALAST = ACUR + 32, ATMP = ALAST + 32; // u32[8] each: reachable flags per position as bit sets (see the kernel)
-		static constexpr uint32_t GCTX = ATMP + 32;                                   // PosGroupCtx
+		// u32[8], 16-lane groups only (the 8-lane build has no LDS left: it enumerates all parents): the dead flags of the most recent 256 states as a bit set (bit =
+		// state index mod 256), written -- set or cleared -- for every new state where the pruning loop decides it; what lets a record enumerate LIVE parents only
+		// (-DKAMD_TEST_DEAD_WINDOW=32: a test build of the lane emulator that looks 32 states back, so that its runs take the walk through the arena that a
+		// longer range falls back to)
+#ifdef KAMD_TEST_DEAD_WINDOW
+		static constexpr uint32_t DWIN_BITS = KAMD_TEST_DEAD_WINDOW;
+#else
+		static constexpr uint32_t DWIN_BITS = 256;
+#endif
+		static constexpr uint32_t DWIN = ATMP + 32, DWIN_WORDS = DWIN_BITS / 32;
+		static constexpr uint32_t GCTX = DWIN + (G == 16 ? 32 : 0);                   // PosGroupCtx
 		static constexpr uint32_t RINFO = GCTX + 64;                                  // u32[G]: per record of the pass -- first incoming state | start states << 27 ... see the kernel
 		static constexpr uint32_t PBEST = RINFO;                                      // f32[G], after the rounds (the records' entries are dead then): per node of the position the best socket-free score of the common root (pruning)
 		static constexpr uint32_t OVFL = RINFO + 4 * G;                               // u32: a state of this group did not fit (arena / staging)
@@ -71,7 +80,7 @@
 #else
 		static constexpr uint32_t CHR = TYPR + 4 * PHR, SIZE = (CHR + 8 * PHR + 15) & ~15u;     // u32[2 * PHR]: the next two nodes of their LM node's back-off chain (ModelView::lmChain)
 #endif
-		// shared by the wavefront: per item lane of a round the lane of its record | the lane (in the row) its record's first item sits at << 8 | the record's item count - 1 << 12;
+		// shared by the wavefront: per lane of a round that a record's FIRST item takes (the lane of the record | this lane << 6) + 1, else 0;
 		// after the steps (G == 8): the list of the chunks that go on in the general search
 		static constexpr uint32_t ROWMAP = (64 / G) * SIZE, TOTAL = ROWMAP + 128;
 	};
@@ -85,8 +94,8 @@
 	enum : uint32_t { PSB_PASS1 = 0x1000 };
 	// developer statistics of a host (lane-emulated) build with -DKAMD_POSSTATS: how full the rounds of k_pos_path are, printed at exit
 #if defined(KAMD_POSSTATS) && defined(KAMD_HIPEMU)
-	struct PosStats { std::atomic<unsigned long long> c[24]; ~PosStats() { fprintf(stderr, "[posstats] waveSteps %llu groupSteps %llu rounds %llu bigRounds %llu itemLanes %llu deadParents %llu scored %llu kept %llu multiChunkItems %llu roundsWithMulti %llu argmaxIters %llu reps %llu lmCalls %llu retries %llu rowsUsed %llu zItems %llu sockItems %llu testSteps %llu testChunks %llu\n",
-		c[0].load(), c[1].load(), c[2].load(), c[3].load(), c[4].load(), c[5].load(), c[6].load(), c[7].load(), c[8].load(), c[9].load(), c[10].load(), c[11].load(), c[12].load(), c[13].load(), c[14].load(), c[15].load(), c[16].load(), c[17].load(), c[18].load()); } };
+	struct PosStats { std::atomic<unsigned long long> c[24]; ~PosStats() { fprintf(stderr, "[posstats] waveSteps %llu groupSteps %llu rounds %llu bigRecords %llu itemLanes %llu deadParents %llu scored %llu kept %llu multiChunkItems %llu roundsWithMulti %llu argmaxIters %llu reps %llu lmCalls %llu retries %llu rowsUsed %llu zItems %llu sockItems %llu testSteps %llu testChunks %llu straddled %llu arenaSelects %llu roundsPerStep %.4f\n",
+		c[0].load(), c[1].load(), c[2].load(), c[3].load(), c[4].load(), c[5].load(), c[6].load(), c[7].load(), c[8].load(), c[9].load(), c[10].load(), c[11].load(), c[12].load(), c[13].load(), c[14].load(), c[15].load(), c[16].load(), c[17].load(), c[18].load(), c[19].load(), c[20].load(), c[0].load() ? (double)c[2].load() / (double)c[0].load() : 0.0); } };
 	static PosStats gPosStats;
 	struct PosHist { std::atomic<unsigned long long> h[6][70]; ~PosHist() { static const char* nm[6] = { "nRec", "nodes", "newStates", "itemsPerRecord", "parentAge", "nodeDist" }; for (int a = 0; a < 6; ++a) { fprintf(stderr, "[poshist] %s:", nm[a]); for (int b = 0; b < 70; ++b) if (h[a][b].load()) fprintf(stderr, " %d:%llu", b, h[a][b].load()); fprintf(stderr, "\n"); } } };
 	static PosHist gPosHist;
@@ -145,6 +154,25 @@
 		if constexpr (G == 16) return rowMaxU16(v);
 		else { uint32_t o; o = __shfl_xor(v, 4, 8); v = o > v ? o : v; o = __shfl_xor(v, 2, 8); v = o > v ? o : v; o = __shfl_xor(v, 1, 8); v = o > v ? o : v; return v; }
 	}
+	__device__ __forceinline__ void ldsAnd(LDS_AS uint32_t* p, uint32_t v)      // ds_and_b32 (no return value)
+	{
+#if defined(__HIP_DEVICE_COMPILE__)
+		__hip_atomic_fetch_and(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#else
+		__atomic_fetch_and((uint32_t*)p, v, __ATOMIC_RELAXED);
+#endif
+	}
+	// position of the k-th (from 0) set bit of v (v has more than k set bits): five popcounts
+	__device__ __forceinline__ uint32_t nthSetBit(uint32_t v, uint32_t k)
+	{
+		uint32_t pos = 0, c;
+		c = (uint32_t)__popc(v & 0xFFFFu); if (k >= c) { k -= c; pos += 16; v >>= 16; }
+		c = (uint32_t)__popc(v & 0xFFu); if (k >= c) { k -= c; pos += 8; v >>= 8; }
+		c = (uint32_t)__popc(v & 0xFu); if (k >= c) { k -= c; pos += 4; v >>= 4; }
+		c = (uint32_t)__popc(v & 0x3u); if (k >= c) { k -= c; pos += 2; v >>= 2; }
+		if (k >= (v & 1u)) pos += 1;
+		return pos;
+	}
 	__device__ __forceinline__ void ldsMaxF(LDS_AS float* p, float v)      // ds_max_f32 (no return value)
 	{
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -192,6 +220,9 @@
 		static_assert(G == 16 || G == 8, "a lane group is one DPP row or half of one");
 		using PosLay = PosLayT<G>;
 		constexpr uint32_t NG = 64 / G, GM = (1u << G) - 1u, PST_CAP = PosLay::PST_CAP, PHR = PosLay::PHR;
+		// Records enumerate the LIVE states of their predecessor range only (16-lane groups): an item of a pruned parent would load it, find it dead and leave --
+		// 15 % of the item lanes of the benchmark corpus.  A dead parent contributes to no output and the live ones keep their order, so nothing else changes.
+		constexpr bool kLiveOnly = G == 16;
 		// passes of G records a position's records go through: two for an 8-lane group (16 records, as in round 5); for a 16-lane group one -- and two in the typo
 		// compilations (32 records: the alternatives of a typo bring many candidates to one place; 8 of c5's 8 192 chunks had such a position and finished in the
 		// general search, 0.3 ms behind everything else)
@@ -201,9 +232,9 @@
 		constexpr uint32_t kP = 16 / G;
 #endif
 		// gl / grp: lane in its group / the group (the bookkeeping of a step).  The ITEMS of a round sit in the four 16-lane DPP rows of the wavefront whatever
-		// the group width is: il / ishift = lane in its row / the row's first lane.
+		// the group width is: il / irow = lane in its row / the row.
 		const uint32_t lane = threadIdx.x, gl = lane & (uint32_t)(G - 1), gshift = lane & (uint32_t)(64 - G), grp = lane / (uint32_t)G, lds = grp * PosLay::SIZE;
-		const uint32_t il = lane & 15u, ishift = lane & 48u, irow = lane >> 4; (void)ishift;
+		const uint32_t il = lane & 15u, irow = lane >> 4;
 		LDS_AS uint32_t* rBeg = ldsPtr<uint32_t>(lds + PosLay::RBEG);
 		LDS_AS uint32_t* rEnd = ldsPtr<uint32_t>(lds + PosLay::REND);
 		LDS_AS uint32_t* rCum = ldsPtr<uint32_t>(lds + PosLay::RCUM);
@@ -236,18 +267,15 @@
 #define WBALLOT(p) hipemu_ballot64(p)
 #define WSHFL(v, l) hipemu_shfl64((v), (int)(l))
 #define WREADLANE(v, l) hipemu_shfl64((v), (int)(l))
-#define ISHFL16(v, l) hipemu_shfl64((v), (int)(ishift + ((uint32_t)(l) & 15u)))
 #define IROR(N, v) ((uint32_t)hipemu_row_ror64((int)(v), (N)))
 #define IRORF(N, v) __uint_as_float((uint32_t)hipemu_row_ror64((int)__float_as_uint(v), (N)))
 #else
 #define WBALLOT(p) ((unsigned long long)__ballot(p))
 #define WSHFL(v, l) __shfl((v), (int)(l), 64)
 #define WREADLANE(v, l) ((uint32_t)__builtin_amdgcn_readlane((int)(v), (int)(l)))      // the source lane is the same for the whole wavefront: v_readlane_b32, no LDS round trip
-#define ISHFL16(v, l) __shfl((v), (int)(l), 16)
 #define IROR(N, v) rowRor<N>(v)
 #define IRORF(N, v) rowRorF<N>(v)
 #endif
-#define IBALLOT16(p) ((uint32_t)((WBALLOT(p) >> ishift) & 0xFFFFu))
 		// developer aid (KAMD_POS_DEBUG builds + KAMD_HANGDUMP=1): where a lane group is, readable from the host while the kernel runs
 #ifdef KAMD_POS_DEBUG
 #define PBEACON(code, a, b2, c2) { if (W.beacon && mine && gl == 0) { uint32_t* bq_ = W.beacon + 64ull * chunk; __builtin_nontemporal_store((uint32_t)(code), bq_); __builtin_nontemporal_store((uint32_t)(a), bq_ + 1); __builtin_nontemporal_store((uint32_t)(b2), bq_ + 2); __builtin_nontemporal_store((uint32_t)(c2), bq_ + 3); } }
@@ -294,7 +322,7 @@
 		// one position, so the propagation runs over positions: reachable(x) <=> one of the (<= 4 distinct) start positions of x's nodes is reachable.
 		const bool canPropagate = nPos <= 255 && active && desc[0].nNodes == 0;
 		bool scanned = false;
-		if (gl < 8) { aCur[gl] = gl == 0 ? 1u : 0u; aLast[gl] = 0; }
+		if (gl < 8) { aCur[gl] = gl == 0 ? 1u : 0u; aLast[gl] = 0; if constexpr (kLiveOnly) ldsPtr<uint32_t>(lds + PosLay::DWIN)[gl] = 0; }
 		for (uint32_t k = gl; k < 16; k += G) gctx[k] = 0;
 		rinfo[gl] = 0; if (gl == 0) *ovfL = 0;
 
@@ -385,7 +413,7 @@
 				rqp[0] = rqA;
 				if constexpr (kP > 1) if (nRec > (uint32_t)G && gl + G < nRec) rqp[kP - 1] = recs[firstRec + G + gl].rq;      // (a second pass: fetched here, off the first pass's chain)
 				// ---- nodes of the position (lane j = node i0 + j): incoming state range and live count from the ring ----
-				uint32_t pBeg = 0, nP = 0; bool bad = false; uint32_t why = 0;
+				uint32_t pBeg = 0, nP = 0, nLv = 0; bool bad = false; uint32_t why = 0;      // (nLv: the live ones among the nP incoming states)
 				if (gl < m)
 				{
 					const uint32_t fp = ppA & 0xFFFFu, lp = fp + ((ppA >> 16) & 0xFFu);
@@ -396,6 +424,7 @@
 						nP = rEnd[lp & (RING - 1)] - pBeg;
 						const uint32_t nLive = rCum[lp & (RING - 1)] - (fp ? rCum[(fp - 1) & (RING - 1)] : 0u);
 						if (nLive > P.smallMax) { bad = true; why = 3; }      // medium / large path container (BestPathContainer.hpp:275-277)
+						nLv = nLive;
 					}
 				}
 				nCnt[gl] = 0;
@@ -406,8 +435,11 @@
 				{
 					const uint32_t rq = rqp[ps_];
 					const uint32_t nlR = (rq >> 8) & 0xFFu, Rr = rq & 0xFFu;
-					const uint32_t nPk = GSHFL(nP, nlR), pBegR = GSHFL(pBeg, nlR);
+					const uint32_t nPk = GSHFL(kLiveOnly ? nLv : nP, nlR), pBegR = GSHFL(pBeg, nlR);
 					const uint32_t Q = ps_ * G + gl < nRec ? nPk * Rr : 0u;
+#if defined(KAMD_POSSTATS) && defined(KAMD_HIPEMU)
+					{ const uint32_t nAll = GSHFL(nP, nlR); if (kLiveOnly && ps_ * G + gl < nRec && !bad) PSTAT(5, (nAll - nPk) * Rr) }
+#endif
 					if (Q > PBIG_CAP || pBegR >= (1u << 27)) { bad = true; why = 4; }
 					Qp[ps_] = Q; pBegRp[ps_] = pBegR;
 					if (ps_ * G + gl < nRec) PHIST(3, Q)
@@ -493,7 +525,7 @@
 #else
 						gctx[14] = 0;
 #endif
-						gctx[15] = (blockIdx.x * NG + grp) * PBIG_CAP;
+						gctx[15] = 0;
 						*ovfL = 0;
 					}
 					posStart = stTop;
@@ -522,8 +554,8 @@
 			const uint32_t Qw = active ? ((kP > 1 && pass) ? Qp[kP - 1] : Qp[0]) : 0u;
 
 			// ================= the wavefront: the items of all four positions, packed into its lanes =================
-			// Records in lane order (group 0's, then group 1's ...), a record whole in one 16-lane row; up to four rows are scored together.  A record
-			// of more than 16 items gets the wavefront to itself (its items one per lane, settled by scanning instead of rotations).
+			// Records in lane order (group 0's, then group 1's ...).  A round is the next up to 64 items: the longest prefix of the remaining records whose
+			// items fit the wavefront, one item per lane, whatever 16-lane rows a record falls in (a record has at most PBIG_CAP = 64 items, so it always fits).
 			{
 				uint32_t S16 = Qw;
 				{ uint32_t t; t = IROR(1, S16); S16 += il >= 1 ? t : 0u; t = IROR(2, S16); S16 += il >= 2 ? t : 0u; t = IROR(4, S16); S16 += il >= 4 ? t : 0u; t = IROR(8, S16); S16 += il >= 8 ? t : 0u; }
@@ -535,53 +567,38 @@
 				{
 					const unsigned long long nz = nzAll & ~((1ull << recDoneW) - 1ull);
 					if (!nz) break;
-					if (++guardW > 80u) { *ovfL = 1; break; }      // (belt and braces: every pass takes at least one record)
-					const uint32_t first = (uint32_t)__ffsll((unsigned long long)nz) - 1u;
-					const uint32_t Qfirst = WREADLANE(Qw, first);
-					const bool bigMode = Qfirst > 16u;
-					int myRow = -1; uint32_t myStart = 0, nRows = 0, myItemsRow = 0;
-					if (bigMode) { recDoneW = first + 1; baseW = WREADLANE(Winc, first); }
-					else
-					{
-						for (uint32_t b = 0; b < 4; ++b)
-						{
-							const bool take = lane >= recDoneW && Winc - baseW <= 16u;      // a prefix of the remaining records (Winc is non-decreasing; a record of > 16 ends it)
-							const unsigned long long tm = WBALLOT(take);
-							const uint32_t n = (uint32_t)__popcll(tm);
-							if (!n) break;
-							if (take) { myRow = (int)b; myStart = Winc - Qw - baseW; }
-							const uint32_t it = WREADLANE(Winc, recDoneW + n - 1) - baseW;
-							if (irow == b) myItemsRow = it;
-							baseW += it; recDoneW += n; nRows = b + 1;
-							if (recDoneW >= 64) break;
-						}
-					}
+					if (++guardW > 80u) { *ovfL = 1; break; }      // (belt and braces: every round takes at least one record)
+					const bool take = lane >= recDoneW && Winc - baseW <= 64u;      // a prefix of the remaining records (Winc is non-decreasing; baseW = the items of the records done)
+					const uint32_t n = (uint32_t)__popcll(WBALLOT(take));
+					if (!n) { *ovfL = 1; break; }      // (cannot happen: the first remaining record has at most 64 items)
+					const uint32_t nItems = WREADLANE(Winc, recDoneW + n - 1) - baseW;
+					const uint32_t myStart = Winc - Qw - baseW;      // wavefront lane of this record's first item
 					PTL(2)
-					if (lane == 0) { PSTAT(2, 1) PSTAT(3, bigMode ? 1 : 0) PSTAT(14, bigMode ? 4 : nRows) }
-					// ---- item (row = this lane's 16-lane row, offset = lane in row) -> its record's lane ----
-					const uint32_t q = bigMode ? lane : il;
-					bool valid; uint32_t recLane, local, lastK = 0;      // lastK: lane (in the row) of the record's last item
-					if (!bigMode)
-					{
-						// every record marks the lane of its row that its FIRST item takes with (its lane | that lane << 8 | its item count - 1 << 12) + 1; an item
-						// lane finds its record's mark by filling the marks forward along the row (four row steps), and leaves its entry cleared for the next round
-						if (myRow >= 0 && Qw) rowMap[16 * (uint32_t)myRow + myStart] = (uint16_t)((lane | (myStart << 8) | ((Qw - 1u) << 12)) + 1u);
-						__syncthreads();
-						valid = irow < nRows && il < myItemsRow;
-						uint32_t e = rowMap[lane];
-						rowMap[lane] = 0;
-						{ uint32_t o;
-						  o = IROR(1, e); e = (e == 0 && il >= 1) ? o : e;
-						  o = IROR(2, e); e = (e == 0 && il >= 2) ? o : e;
-						  o = IROR(4, e); e = (e == 0 && il >= 4) ? o : e;
-						  o = IROR(8, e); e = (e == 0 && il >= 8) ? o : e; }
-						e = e ? e - 1u : 0u;
-						recLane = valid ? (e & 0xFFu) : lane;
-						local = valid ? il - ((e >> 8) & 15u) : 0u;
-						lastK = valid ? ((e >> 8) & 15u) + (e >> 12) : il;
-					}
-					else { valid = lane < Qfirst; recLane = valid ? first : lane; local = lane; }
-					const uint32_t startK = q - local;      // (lane of the record's first item)
+					if (lane == 0) { PSTAT(2, 1) PSTAT(14, (nItems + 15u) >> 4) }
+					if (take && Qw) { if (Qw > 16u) PSTAT(3, 1) if ((myStart >> 4) != ((myStart + Qw - 1u) >> 4)) PSTAT(19, 1) }
+					// ---- item (= wavefront lane) -> its record's lane: every record marks the lane its FIRST item takes with (its lane | that lane << 6) + 1; an
+					// item lane finds its record's mark by filling the marks forward -- along its row (four row steps), then across the rows from lanes 15, 31
+					// and 47 (wave-uniform sources) --, leaves its entry cleared for the next round and fetches the item count from the record's lane ----
+					if (take && Qw) rowMap[myStart] = (uint16_t)((lane | (myStart << 6)) + 1u);
+					baseW += nItems; recDoneW += n;
+					__syncthreads();
+					bool valid = lane < nItems;
+					uint32_t e = rowMap[lane];
+					rowMap[lane] = 0;
+					{ uint32_t o;
+					  o = IROR(1, e); e = (e == 0 && il >= 1) ? o : e;
+					  o = IROR(2, e); e = (e == 0 && il >= 2) ? o : e;
+					  o = IROR(4, e); e = (e == 0 && il >= 4) ? o : e;
+					  o = IROR(8, e); e = (e == 0 && il >= 8) ? o : e;
+					  o = WREADLANE(e, 15); e = (e == 0 && irow == 1) ? o : e;
+					  o = WREADLANE(e, 31); e = (e == 0 && irow == 2) ? o : e;
+					  o = WREADLANE(e, 47); e = (e == 0 && irow == 3) ? o : e; }
+					e = e ? e - 1u : 0u;
+					const uint32_t recLane = valid ? (e & 63u) : lane;
+					const uint32_t startK = valid ? (e >> 6) : lane;      // (lane of the record's first item)
+					const uint32_t Qrec = WSHFL(Qw, recLane);
+					const uint32_t lastK = valid ? startK + Qrec - 1u : lane;      // (lane of the record's last item: the record's later items may belong to the next row)
+					const uint32_t local = lane - startK;
 					// ---- the owner group's side ----
 					const uint32_t owner = recLane / (uint32_t)G, k = recLane & (uint32_t)(G - 1), ldsO = owner * PosLay::SIZE;
 					const uint4 g0 = ldsLoad4(ldsO + PosLay::GCTX), g1 = ldsLoad4(ldsO + PosLay::GCTX + 16), g2 = ldsLoad4(ldsO + PosLay::GCTX + 32), g3 = ldsLoad4(ldsO + PosLay::GCTX + 48);
@@ -589,7 +606,7 @@
 					const uint8_t* uniqO = reinterpret_cast<const uint8_t*>((uint64_t)g1.x | ((uint64_t)g1.y << 32));
 					const float* nodeTypoO = reinterpret_cast<const float*>((uint64_t)g1.z | ((uint64_t)g1.w << 32)); (void)nodeTypoO;
 					const uint32_t stCapO = g2.x, stTopO = g2.y, posStartO = g2.z, ringTopO = g2.w;
-					const uint32_t retry0O = g3.y & 0xFFFFu, retry1O = g3.y >> 16, bigBaseO = g3.w;
+					const uint32_t retry0O = g3.y & 0xFFFFu, retry1O = g3.y >> 16;
 					CONG_ONLY(const uint32_t ofNodesO = g3.z;)
 					const uint32_t ri = ldsPtr<uint32_t>(ldsO + PosLay::RINFO)[k];
 					const uint32_t pBegK = ri & 0x7FFFFFFu, R = ri >> 27;
@@ -625,10 +642,34 @@
 					uint32_t pch1 = 0, pch2 = 0, nch1 = 0, nch2 = 0;      // back-off chain of the parent's LM node / of the item's new one
 #endif
 					if (valid) PSTAT(4, 1)
+					// the parent: state pBegK + p -- or (live parents only) the p-th LIVE state from pBegK on, selected by popcounts over the owner group's dead-bit
+					// window; a range that reaches behind the window (or bits a discarded attempt's states have overwritten: ringTop is the high-water mark) is
+					// walked in the arena instead -- slow and rare
+					uint32_t pidx = pBegK + p;
+					if constexpr (kLiveOnly) if (valid)
+					{
+						uint32_t k = p;
+						if (ringTopO - pBegK <= PosLay::DWIN_BITS)
+						{
+							LDS_AS uint32_t* dw = ldsPtr<uint32_t>(ldsO + PosLay::DWIN);
+							uint32_t w = pBegK >> 5;
+							uint32_t v = ~dw[w & (PosLay::DWIN_WORDS - 1u)] & (0xFFFFFFFFu << (pBegK & 31u));
+							uint32_t c = (uint32_t)__popc(v);
+							for (uint32_t it = 0; k >= c && it < PosLay::DWIN_WORDS; ++it) { k -= c; ++w; v = ~dw[w & (PosLay::DWIN_WORDS - 1u)]; c = (uint32_t)__popc(v); }
+							pidx = k < c ? (w << 5) + nthSetBit(v, k) : pBegK;      // (k < c always: the record's item count is the range's live count)
+						}
+						else
+						{
+							PSTAT(20, 1)
+							uint32_t idx = pBegK;
+							for (; idx + 1 < posStartO; ++idx) { if (!loadHot(stO, idx).dead()) { if (!k) break; --k; } }
+							pidx = idx;
+						}
+					}
 					if (valid)
 					{
 						// what the step reads of its parent state: from the LDS ring of the last PHR states, else (older) from the arena
-						const uint32_t pidx = pBegK + p, slot = pidx & (PHR - 1);
+						const uint32_t slot = pidx & (PHR - 1);
 						PHIST(4, ringTopO - pidx)
 						Hot ps;
 						if (ringTopO - pidx <= PHR)
@@ -663,13 +704,13 @@
 						CONG_ONLY(float icDeferred = 0;)
 						do
 						{
-							if (ps.dead()) { PSTAT(5, 1) valid = false; break; }
+							if (ps.dead()) { if (!kLiveOnly) PSTAT(5, 1) valid = false; break; }
 							if (isZ) PSTAT(15, 1)
 							if (csock) PSTAT(16, 1)
 							if (isZ)
 							{
 								// z-coda / z-siot shortcut (PathEvaluator.hpp:389-432): the path is copied iff its last morpheme's tag admits the shortcut
-								const uint8_t lastTag = M.morphs[stO[pBegK + p].wid].tag;
+								const uint8_t lastTag = M.morphs[stO[pidx].wid].tag;
 								if (!((uint8_t)c.secondWid == T_Z_CODA ? (isJClass(lastTag) || isEClass(lastTag)) : isNNClass(lastTag))) { valid = false; break; }
 								cand = ps.accScore + c.additional * P.typoCostWeight;
 								lmNode = (int32_t)local;      // (every copy is its own state: the key is the item)
@@ -693,18 +734,18 @@
 								}
 							}
 #ifdef KAMD_CONG
-							if (csock && !single) { firstWid = M.morphs[M.morphs[stO[pBegK + p].wid].combinedId].lmId; widReplaced = true; }
+							if (csock && !single) { firstWid = M.morphs[M.morphs[stO[pidx].wid].combinedId].lmId; widReplaced = true; }
 #else
 							if (csock && !single)
 							{
 								// the reference keeps the combined word id of the latest matching split stem for all later predecessors (PathEvaluator.hpp:578-591)
-								for (int32_t pp = (int32_t)p; pp >= 0; --pp)
+								for (uint32_t qi = pidx + 1; qi-- > pBegK; )
 								{
-									const Hot qs = loadHot(stO, pBegK + pp);
+									const Hot qs = loadHot(stO, qi);
 									if (qs.dead() || !qs.socket() || qs.socket() != csock) continue;
 									if ((qs.leftFeat() & LF_PREV_ZSIOT) && (!isNNClass(ctag) || spaceBefore)) continue;
 									if (spaceBefore && !(P.spaceTol > 0)) continue;
-									firstWid = M.morphs[M.morphs[stO[pBegK + pp].wid].combinedId].lmId; widReplaced = true;
+									firstWid = M.morphs[M.morphs[stO[qi].wid].combinedId].lmId; widReplaced = true;
 									break;
 								}
 							}
@@ -785,11 +826,10 @@
 
 					// writes the state of a key's winner -- item `wl` of this round's record k -- at arena slot `pos`
 					// (wx1, wx2: CoNgram -- the winner's context id; Knlm -- the next two nodes of the new LM node's back-off chain)
-					auto emitState = [&](uint32_t pos, bool ring, int32_t wNode, uint8_t wSp, uint8_t wRoot, float wscore, float wfcs, float wtyp, uint32_t wx1, uint32_t wx2, uint32_t wl)
+					auto emitState = [&](uint32_t pos, bool ring, int32_t wNode, uint8_t wSp, uint8_t wRoot, float wscore, float wfcs, float wtyp, uint32_t wx1, uint32_t wx2, uint32_t wl, uint32_t parent)
 					{
 						const uint32_t rslot = pos & (PHR - 1);
-						uint32_t parent = pBegK + wl, wr = 0;
-						if (R != 1) { parent = pBegK + wl / R; wr = wl % R; }
+						const uint32_t wr = R != 1 ? wl % R : 0u;
 						const uint32_t rel = pos - posStartO;
 						if (isZ)
 						{
@@ -856,82 +896,47 @@
 							| (nl << 8) | ((rc.w & PR_PASS1) ? (uint32_t)PSB_PASS1 : 0u));
 					};
 					const uint32_t keyLo = (uint32_t)rKey, keyHi = (uint32_t)(rKey >> 32);
-					bool rep; float best, wfcs, wtyp; uint32_t wl, wx1, wx2, wNodeU, wHi;
-					if (!bigMode)
+					bool rep; float best, wfcs, wtyp; uint32_t wl, wx1, wx2, wNodeU, wHi, wpar;
 					{
 						// ---- per key: its representative (the key's first item, which emits the state) and its winner (best score, first item on ties).
 						// Items of one record that share a key are settled together: every record takes the key of its first unsettled item, the items
-						// carrying it find their best by a segmented scan over the row (segments = records, four steps), and the representative fetches it
-						// from the record's last lane.  One pass per distinct key of a record -- usually one or two, where all-pairs rotations took 15. ----
-						rep = false; best = rScore; uint32_t qw = q;
-						const uint32_t recMask = ((2u << (lastK - startK)) - 1u) << startK;
+						// carrying it find their best by a segmented scan over the wavefront (segments = records: four steps along the row, then the pair at
+						// the last lane of every row is carried into the lanes of the next row whose record began before it -- the lower lane wins on
+						// equal scores throughout), and the representative fetches it from the record's last lane.  One pass per distinct key of a record
+						// -- usually one or two. ----
+						rep = false; best = rScore; uint32_t qw = lane;
+						const unsigned long long recMask = ((2ull << (lastK - startK)) - 1ull) << startK;
 						bool un = valid;
-						while (WBALLOT(un))
+						for (;;)
 						{
+							const unsigned long long unAll = WBALLOT(un);
+							if (!unAll) break;
 							if (lane == 0) PSTAT(10, 1)
-							const uint32_t mine = IBALLOT16(un) & recMask;
-							const uint32_t f = mine ? (uint32_t)__ffs((int)mine) - 1u : q;
-							const uint32_t kLo = ISHFL16(keyLo, f), kHi = ISHFL16(keyHi, f);
+							const unsigned long long mine = unAll & recMask;
+							const uint32_t f = mine ? (uint32_t)__ffsll(mine) - 1u : lane;
+							const uint32_t kLo = WSHFL(keyLo, f), kHi = WSHFL(keyHi, f);
 							const bool match = un & (keyLo == kLo) & (keyHi == kHi);
-							float bs = match ? rScore : -3.0e38f; uint32_t bi = q;
-#define KAMD_POS_SEG(N) { const float os = IRORF(N, bs); const uint32_t oi = IROR(N, bi); const bool take = (q >= startK + N) & (os >= bs); bs = take ? os : bs; bi = take ? oi : bi; }
+							float bs = match ? rScore : -3.0e38f; uint32_t bi = lane;
+#define KAMD_POS_SEG(N) { const float os = IRORF(N, bs); const uint32_t oi = IROR(N, bi); const bool take = (il >= N) & (lane >= startK + N) & (os >= bs); bs = take ? os : bs; bi = take ? oi : bi; }
 							KAMD_POS_SEG(1) KAMD_POS_SEG(2) KAMD_POS_SEG(4) KAMD_POS_SEG(8)
 #undef KAMD_POS_SEG
-							const float rb = ISHFL16(bs, lastK); const uint32_t rq = ISHFL16(bi, lastK);
-							if (match && q == f) { rep = true; best = rb; qw = rq; }
+#define KAMD_POS_CARRY(ROW) { const float os = __uint_as_float(WREADLANE(__float_as_uint(bs), 16 * ROW - 1)); const uint32_t oi = WREADLANE(bi, 16 * ROW - 1); const bool take = (irow == ROW) & (startK < 16u * ROW) & (os >= bs); bs = take ? os : bs; bi = take ? oi : bi; }
+							KAMD_POS_CARRY(1) KAMD_POS_CARRY(2) KAMD_POS_CARRY(3)
+#undef KAMD_POS_CARRY
+							const float rb = WSHFL(bs, lastK); const uint32_t rq = WSHFL(bi, lastK);
+							if (match && lane == f) { rep = true; best = rb; qw = rq; }
 							un = un && !match;
 						}
 						PTL(5)
-						wfcs = ISHFL16(rFcs, qw);
-						wtyp = ISHFL16(rTypo, qw);
+						wfcs = WSHFL(rFcs, qw);
+						wtyp = WSHFL(rTypo, qw);
 #ifdef KAMD_CONG
-						wx1 = ISHFL16(ctx, qw); wx2 = 0;
+						wx1 = WSHFL(ctx, qw); wx2 = 0;
 #else
 						wx1 = nch1; wx2 = nch2;      // (the winner has this item's key, hence its LM node)
 #endif
 						wl = qw - startK; wNodeU = (uint32_t)lmNode; wHi = keyHi;
-					}
-					else
-					{
-						// ---- a record of more than 16 items: every item finds the representative (first item) and the winner (best score, first on ties) of its
-						// key by scanning the staged list ----
-						PosBigItem* big = reinterpret_cast<PosBigItem*>(W.posBig) + bigBaseO;
-						if (lane < Qfirst)
-						{
-							PosBigItem it; it.keyLo = keyLo; it.keyHi = keyHi; it.score = rScore; it.fcs = rFcs;
-#ifdef KAMD_CONG
-							it.ctx = ctx;
-#else
-							it.ctx = 0;
-#endif
-							big[lane] = it;
-						}
-						__syncthreads();
-						rep = false; best = 0; uint32_t qw = lane;
-						if (lane < Qfirst && (keyLo & keyHi) != 0xFFFFFFFFu)
-						{
-							rep = true; bool have = false;
-							for (uint32_t j = 0; j < Qfirst; ++j)
-							{
-								if (big[j].keyLo != keyLo || big[j].keyHi != keyHi) continue;
-								if (j < lane) { rep = false; break; }
-								const float sj = big[j].score;
-								if (!have || sj > best) { best = sj; qw = j; have = true; }
-							}
-						}
-						wfcs = 0; wtyp = 0; wx1 = 0; wx2 = 0;
-						if (rep)
-						{
-							wfcs = big[qw].fcs;
-							wtyp = stO[pBegK + (R > 1 ? qw / R : qw)].accTypoCost;
-#ifdef KAMD_CONG
-							wx1 = big[qw].ctx;
-#else
-							if (!isZ) { const uint2 nc = *reinterpret_cast<const uint2*>(M.lmChain + 2 * (size_t)keyLo); wx1 = nc.x; wx2 = nc.y; }
-#endif
-						}
-						wl = qw; wNodeU = keyLo; wHi = keyHi;
-						__syncthreads();      // (the staged list is free again)
+						wpar = WSHFL(pidx, qw);      // (the winner's parent state)
 					}
 					// ---- kept states stream to their group's arena, in item order ----
 					uint32_t myRank = 0, myAdd = 0, ownerAdd = 0;
@@ -947,7 +952,7 @@
 						const uint32_t pos = stTopO + myRank;
 						// (the winner is an item of the same record: same candidate, same node, same key.  The LDS ring keeps the LAST PHR states: of more
 						// than PHR states written in one round only those go into it, so that two lanes never write one slot)
-						if (pos < stCapO && pos - posStartO < PST_CAP) emitState(pos, pos + PHR >= stTopO + ownerAdd, (int32_t)wNodeU, (uint8_t)wHi, (uint8_t)(wHi >> 8), best, wfcs, wtyp, wx1, wx2, wl);
+						if (pos < stCapO && pos - posStartO < PST_CAP) emitState(pos, pos + PHR >= stTopO + ownerAdd, (int32_t)wNodeU, (uint8_t)wHi, (uint8_t)(wHi >> 8), best, wfcs, wtyp, wx1, wx2, wl, wpar);
 						else ldsPtr<uint32_t>(ldsO + PosLay::OVFL)[0] = 1;
 					}
 					stTop += myAdd;
@@ -1002,6 +1007,11 @@
 						}
 					}
 					// (the ring copy only if the slot is still this state's: a step may write more than PHR states)
+					if constexpr (kLiveOnly)
+					{
+						LDS_AS uint32_t* dwp = ldsPtr<uint32_t>(lds + PosLay::DWIN) + (((posStart + i) >> 5) & (PosLay::DWIN_WORDS - 1u));
+						if (kill) ldsOr(dwp, 1u << ((posStart + i) & 31u)); else ldsAnd(dwp, ~(1u << ((posStart + i) & 31u)));
+					}
 					if (kill) { st[posStart + i].dead = 1; if (ringTop - (posStart + i) <= PHR) ldsPtr<uint32_t>(hotR + 16 * ((posStart + i) & (PHR - 1)) + 12)[0] |= 1u << 16; }
 					ldsAdd(&nCnt[(bits >> 8) & 0xFu], 1u | ((bits & PSB_PASS1) ? 0u : 1u << 8) | (kill ? 0u : 1u << 16) | ((kill || (bits & SB_STATE_SOCKET)) ? 0u : 1u << 24));
 				}
@@ -1285,10 +1295,8 @@
 #undef WBALLOT
 #undef WSHFL
 #undef WREADLANE
-#undef ISHFL16
 #undef IROR
 #undef IRORF
-#undef IBALLOT16
 #undef PBEACON
 #undef PTL
 #undef PSTAT
