@@ -81,7 +81,9 @@ namespace kamd
 				blocks.clear(); bytes = 0;
 			}
 		};
-		DevBlockCache& devCache() { static DevBlockCache c; return c; }
+		// (never destroyed: the buffers of the developer aids have static storage and give their blocks back from their destructors at process exit -- after a
+		// function-local cache object, constructed later than they, would have been destroyed; the blocks themselves were never freed at exit either)
+		DevBlockCache& devCache() { static DevBlockCache* c = new DevBlockCache; return *c; }
 		int currentDevice() { int d = 0; (void)hipGetDevice(&d); return d; }
 
 		struct DevBuf

@@ -48,7 +48,7 @@
 	};
 	constexpr uint32_t PBIG_CAP = 64;      // items of one record beyond which the position is handed over (a round is one wavefront of items, and a record is never split over two rounds)
 	// what the lanes that score a group's items need of the group (its lane 0 keeps it current in LDS): 16 dwords
-	struct PosGroupCtx { uint64_t st, recs, uniq, nodeTypo; uint32_t stCap, stTop, posStart, ringTop, firstRec, retry, ofNodes, pad; };
+	struct PosGroupCtx { uint64_t st, recs, uniq, nodeTypo; uint32_t stCap, stTop, posStart, ringTop, chunk, retry, ofNodes, nNodes; };
 	static_assert(sizeof(PosGroupCtx) == 64, "PosGroupCtx");
 	template<int G> struct PosLayT
 	{
@@ -183,7 +183,7 @@
 #endif
 	}
 
-	// The general search (searchChunk) for a chunk the position steps leave at node `resumeAt`, called by k_pos_path itself (see the end of the kernel).
+	// The general search (searchChunk) for a chunk the position steps leave at node `stopAt & 0xFFFFFF`, called by k_pos_path itself (see the end of the kernel).
 	// A real function: inlined, the general search's code cost the position steps a tenth of their speed (the registers and spills of a kernel are
 	// allocated as a whole).  It reads the kernel's arguments where they are -- the kernarg segment, through scalar loads, like a kernel does -- instead
 	// of taking them as parameters: copies on the caller's stack would be 1.2 KB of scratch memory per LANE of every wave of the launch.  PosKernArgs
@@ -191,17 +191,23 @@
 	// beside it is compared with the one found there, and a mismatch leaves the chunk to k_best_path.
 	struct PosKernArgs { ModelView M; BatchView B; WorkView W; SearchParams P; const uint32_t* chunkOrder; uint32_t nWork; TYPO_ONLY(const float* nodeTypoAll;) CONG_ONLY(CongDev CG;) };
 #ifdef KAMD_HIPEMU
-	__device__ __noinline__ bool continueChunk(const PosKernArgs* A, uint32_t chunk, uint32_t gl, uint32_t grp, uint32_t slot, uint32_t resumeAt, const uint8_t* scratchCheck, const uint32_t* orderCheck, uint32_t nWorkCheck)
+	__device__ __noinline__ void continueChunk(const PosKernArgs* A, uint32_t chunk, uint32_t gl, uint32_t grp, uint32_t slot, uint32_t stopAt, const uint8_t* scratchCheck, const uint32_t* orderCheck, uint32_t nWorkCheck)
 	{
 #else
-	__device__ __noinline__ bool continueChunk(uint32_t chunk, uint32_t gl, uint32_t grp, uint32_t slot, uint32_t resumeAt, const uint8_t* scratchCheck, const uint32_t* orderCheck, uint32_t nWorkCheck)
+	__device__ __noinline__ void continueChunk(uint32_t chunk, uint32_t gl, uint32_t grp, uint32_t slot, uint32_t stopAt, const uint8_t* scratchCheck, const uint32_t* orderCheck, uint32_t nWorkCheck)
 	{
 		// (a callable function is not handed the kernarg segment pointer itself -- the intrinsic folds to null there -- but the pointer to the hidden
 		// arguments, which follow the explicit ones at the next 8-byte boundary; the loads below stay scalar loads)
 		const PosKernArgs* A = (const PosKernArgs*)((const uint8_t*)__builtin_amdgcn_implicitarg_ptr() - ((sizeof(PosKernArgs) + 7) & ~(size_t)7));
 #endif
 		// (the layout assumption is checked on a member of the middle AND the two members behind the structs: a change that moves only the tail is caught too)
-		if (A->W.posScratch != scratchCheck || A->chunkOrder != orderCheck || A->nWork != nWorkCheck) return false;
+		// (it also leaves the chunk's result word -- searched to the end here | why it left the position steps, or still to be searched by k_best_path --, so that
+		// the kernel keeps nothing in registers over the call)
+		if (A->W.posScratch != scratchCheck || A->chunkOrder != orderCheck || A->nWork != nWorkCheck)
+		{
+			if (gl == 0) { A->W.results[chunk].pad = stopAt; *A->W.posHandOver = 1; }
+			return;
+		}
 		const ModelView& M = A->M; const SearchParams& P = A->P; const BatchView& B = A->B; const WorkView& W = A->W;
 		CONG_ONLY(const CongDev& CG = A->CG;)
 		GroupCtx<16> X(M, P);
@@ -210,8 +216,8 @@
 		X.tl = nullptr;
 		TYPO_ONLY(X.typoAll = A->nodeTypoAll; X.nodeTypo = nullptr;)
 		CONG_ONLY(X.CG = &CG; X.outFirst = false;)
-		searchChunk<16>(X, B, W, chunk, resumeAt);
-		return true;
+		searchChunk<16>(X, B, W, chunk, stopAt & 0xFFFFFFu);
+		if (gl == 0) W.results[chunk].pad = kPosChunkDone | (stopAt & 0xFF000000u);      // (bits 24..31: why it left the position steps, developer statistics)
 	}
 
 	template<int G, int WPS>
@@ -285,6 +291,17 @@
 #define PBEACON(code, a, b2, c2)
 #define PTL(k)
 #endif
+		// s_waitcnt vmcnt(0), stated where the loads in flight have arrived on every path that does work -- the compiler then knows so on the other paths too.
+		// The operand in the gfx9-family encoding: vmcnt = bits 3:0 and 15:14 (0: wait for all), expcnt = bits 6:4 and lgkmcnt = bits 11:8 at their maxima (7, 15:
+		// no wait).  On gfx950 vmcnt counts the wave's vector STORES as well as its loads, in issue order: the wait also drains whatever the wave has stored
+		// before it (before the loop: the start node; behind the group phase: nothing of this step yet -- a step's state stores are issued in its rounds and
+		// behind them -- but what the previous step stored, which the wait for this step's records would cover anyway).
+		constexpr int kWaitVm0 = (0 << 0) | (0 << 14) | (7 << 4) | (15 << 8);
+#if defined(__HIP_DEVICE_COMPILE__)
+#define POS_LOADS_ARRIVED() __builtin_amdgcn_s_waitcnt(kWaitVm0)
+#else
+#define POS_LOADS_ARRIVED() (void)0
+#endif
 		const unsigned long long lowerMask64 = (1ull << lane) - 1ull;
 
 		// One chunk per lane group, four per block, no work loop (with one, the hipcc of ROCm 7.2 produced gfx950 code whose outermost back edge never
@@ -293,37 +310,52 @@
 		const uint32_t ci = blockIdx.x * NG + grp;
 		const bool mine = ci < nWork;
 		const uint32_t chunk = mine ? chunkOrder[ci] : chunkOrder[0];
-		DevChunkResult* res = &W.results[chunk];
-		bool active = mine && res->status == CS_OK;
-		if (mine && !active && gl == 0) res->nPaths = 0;
+		bool active = mine && W.results[chunk].status == CS_OK;
+		if (mine && !active && gl == 0) W.results[chunk].nPaths = 0;
 		const bool searching = active;      // this group has a lattice to search (for the epilogue)
 		PBEACON(1, ci, 0, 0)
 		const uint32_t nBase = W.nodeBase[chunk];
 		const uint32_t Gn = W.nNodes[chunk];
-		DevState* st = W.states + W.stateBase[chunk];
 		const uint32_t stCap = (uint32_t)(W.stateBase[chunk + 1] - W.stateBase[chunk]);
-		uint32_t* nodeStOff = W.nodeStateOff + nBase; uint32_t* nodeStCnt = W.nodeStateCnt + nBase; uint16_t* nodeLive = W.tmpIdx + 2ull * nBase;
-		const uint8_t* uniq = B.spStates + B.spOff[chunk];
-		uint8_t* reach = W.reach + nBase;
-		const PosDesc* desc = W.posDesc + nBase;
-		const PosRec* recs = W.posRecs + W.packBase[chunk];
-		const uint32_t* posPrev = W.posPrev + nBase;
-#ifdef KAMD_TYPO
-		const float* nodeTypo = nodeTypoAll + nBase;
-#else
-		const float* nodeTypo = nullptr;
-#endif
-		const uint32_t nPos = active ? desc[0].firstRec : 0u, eosStart = active ? desc[0].pad2 : 0u;      // positions; the position the end node's predecessors end at
-		const uint32_t* posStarts = W.posMask + nBase;
-		TYPO_ONLY(const uint32_t* posStarts2 = posStarts + W.nodeBase[B.nChunks];)      // (start positions five to eight of a position: lattices over typo graphs, k_expand_pos)
+		// A chunk's tables are a kernel argument plus the chunk's offset.  Over the step loop a lane keeps the 32-bit offsets only -- nBase for the per-node tables,
+		// recBase for the records -- and an address is formed where it is used, against the wave-uniform base: a dozen pointers held per lane were 24 VGPRs
+		// for the whole loop, and at three waves per SIMD the step paid for them with scratch reloads (the one of `recs` at its very head, in front of the
+		// records' loads).  The arena, the start states and the nodes' typo costs are written to the group's PosGroupCtx once, here: the lanes that score items
+		// read them there anyway, and so does the group itself (stArena) where it needs the arena inside the loop.
+		// (nodeLive: the chunk's two 16-bit slots per node of WorkView::tmpIdx, of which the live counts take the first Gn -- element 2 * nBase + i, as the
+		// general search reads them when it takes a chunk over)
+		const uint32_t recBase = W.packBase[chunk];
+		auto nodeStOff = [&](uint32_t i) -> uint32_t& { return W.nodeStateOff[nBase + i]; };
+		auto nodeStCnt = [&](uint32_t i) -> uint32_t& { return W.nodeStateCnt[nBase + i]; };
+		auto nodeLive = [&](uint32_t i) -> uint16_t& { return W.tmpIdx[2ull * nBase + i]; };
+		auto reach = [&](uint32_t i) -> uint8_t& { return W.reach[nBase + i]; };
+		auto desc = [&](uint32_t i) -> const PosDesc& { return W.posDesc[nBase + i]; };
+		auto posPrev = [&](uint32_t i) -> const uint32_t& { return W.posPrev[nBase + i]; };
+		auto posStarts = [&](uint32_t i) -> const uint32_t& { return W.posMask[nBase + i]; };
+		auto recs = [&](uint32_t i) -> const PosRec& { return W.posRecs[recBase + i]; };
+		auto stArena = [&]() -> DevState* { return reinterpret_cast<DevState*>(((LDS_AS uint64_t*)gctx)[0]); };
+		auto uniqStates = [&]() -> const uint8_t* { return reinterpret_cast<const uint8_t*>(((LDS_AS uint64_t*)gctx)[2]); };
+		const uint32_t nPos = active ? desc(0).firstRec : 0u, eosStart = active ? desc(0).pad2 : 0u;      // positions; the position the end node's predecessors end at
+		TYPO_ONLY(const uint32_t nBase2 = nBase + W.nodeBase[B.nChunks];)      // (start positions five to eight of a position: lattices over typo graphs, k_expand_pos)
 		// The reference's `reachable` flags (PathEvaluator.hpp:1159-1176, 1286-1299) as bit sets over positions (LDS, up to 256 positions): aCur -- some
 		// node ending at the position carries a set flag now; aLast -- the flags the last disconnected-lattice test left behind (it rewrites the flag of
 		// every later node by propagation; a formless node never sets its own afterwards, so it keeps that value).  A node's predecessors all end at
 		// one position, so the propagation runs over positions: reachable(x) <=> one of the (<= 4 distinct) start positions of x's nodes is reachable.
-		const bool canPropagate = nPos <= 255 && active && desc[0].nNodes == 0;
+		const bool canPropagate = nPos <= 255 && active && desc(0).nNodes == 0;
 		bool scanned = false;
 		if (gl < 8) { aCur[gl] = gl == 0 ? 1u : 0u; aLast[gl] = 0; if constexpr (kLiveOnly) ldsPtr<uint32_t>(lds + PosLay::DWIN)[gl] = 0; }
-		for (uint32_t k = gl; k < 16; k += G) gctx[k] = 0;
+		if (gl == 0)
+		{
+			LDS_AS uint64_t* g64 = (LDS_AS uint64_t*)gctx;
+			for (uint32_t k = 8; k < 16; ++k) gctx[k] = 0;
+			gctx[12] = chunk; gctx[15] = Gn;      // (the end of the search reads the chunk's index and node count back from here: whatever was formed from them above then ends before the loop)
+			g64[0] = (uint64_t)(W.states + W.stateBase[chunk]); g64[1] = 0; g64[2] = (uint64_t)(B.spStates + B.spOff[chunk]);
+#ifdef KAMD_TYPO
+			g64[3] = (uint64_t)(nodeTypoAll + nBase);
+#else
+			g64[3] = 0;
+#endif
+		}
 		rinfo[gl] = 0; if (gl == 0) *ovfL = 0;
 
 		uint32_t stTop = 1, cumLive = 1;
@@ -335,8 +367,9 @@
 			if (gl == 0)
 			{
 				const MorphRec m0 = M.morphs[0];
+				DevState* st = W.states + W.stateBase[chunk];
 				storeState(st, 0, M.h.bosNode, 0.f, 0.f, 0, m0.feat, COMMON_ROOT, 0, 0, m0.prevFlags, 0, 0xFFFFFFFFu, 0, 0.f, 0, 0);
-				nodeStOff[0] = 0; nodeStCnt[0] = 1; nodeLive[0] = 1;
+				nodeStOff(0) = 0; nodeStCnt(0) = 1; nodeLive(0) = 1;
 				rBeg[0] = 0; rEnd[0] = 1; rCum[0] = 1;
 				ldsStore4(hotR, make_uint4((uint32_t)M.h.bosNode, 0u, (uint32_t)m0.feat | ((uint32_t)COMMON_ROOT << 16), (uint32_t)m0.prevFlags << 8));
 				typR[0] = 0.f;
@@ -348,7 +381,7 @@
 				*reinterpret_cast<uint2*>(&st[0].pad0) = make_uint2(c1, c2);
 #endif
 			}
-			for (uint32_t k = gl; k < Gn; k += G) reach[k] = k == 0 ? 1 : 0;
+			for (uint32_t k = gl; k < Gn; k += G) reach(k) = k == 0 ? 1 : 0;
 			if (!nPos) { stopAt = 1u | (8u << 24); active = false; }      // (no position program: the general kernel searches the chunk from its first node)
 		}
 
@@ -360,11 +393,11 @@
 		uint4 recA0 = make_uint4(0, 0, 0, 0), recA1 = recA0, recA2 = recA0, recB0 = recA0, recB1 = recA0, recB2 = recA0;
 		if (active)
 		{
-			dqA = *reinterpret_cast<const uint4*>(desc + 1);
-			if (nPos >= 2) dqB = *reinterpret_cast<const uint4*>(desc + 2);
-			if (gl < ((dqA.x >> 16) & 0xFFu)) ppA = posPrev[(dqA.x & 0xFFFFu) + gl];
-			if (gl < (dqA.z & 0xFFFFu)) rqA = recs[dqA.y + gl].rq;
-			if constexpr (WPS <= 2) if (gl < (dqA.z & 0xFFFFu)) { const uint4* rp0 = reinterpret_cast<const uint4*>(recs + dqA.y + gl); recA0 = rp0[0]; recA1 = rp0[1]; recA2 = rp0[2]; }
+			dqA = *reinterpret_cast<const uint4*>(&desc(1));
+			if (nPos >= 2) dqB = *reinterpret_cast<const uint4*>(&desc(2));
+			if (gl < ((dqA.x >> 16) & 0xFFu)) ppA = posPrev((dqA.x & 0xFFFFu) + gl);
+			if (gl < (dqA.z & 0xFFFFu)) rqA = recs(dqA.y + gl).rq;
+			if constexpr (WPS <= 2) if (gl < (dqA.z & 0xFFFFu)) { const uint4* rp0 = reinterpret_cast<const uint4*>(&recs(dqA.y + gl)); recA0 = rp0[0]; recA1 = rp0[1]; recA2 = rp0[2]; }
 		}
 
 		// attempt 0: form conditions on.  A node whose own candidates yield no state is evaluated again with the conditions turned into a penalty
@@ -373,6 +406,9 @@
 		uint32_t pi = 1, attempt = 0, retry0 = 0, retry1 = 0;
 		uint4 dqC = make_uint4(0, 0, 0, 0); uint32_t ppB = 0, rqB = 0;      // (fetched in a step's first attempt, kept over its retries)
 		uint32_t guardSteps = 0;
+		// (what was fetched above has arrived before the first step: a wait for it inside the loop would be a wait for everything the step has in flight -- the
+		// counter retires in order, and the compiler cannot tell how many of a step's conditional loads stand behind a load from before the loop)
+		POS_LOADS_ARRIVED();
 		__syncthreads();
 
 		while (WBALLOT(active))
@@ -398,20 +434,22 @@
 			}
 			if (active)
 			{
+				// (three waves per SIMD: this step's records are the first loads of the step -- the memory counter retires in order, so the wait for them, at the
+				// end of the group's bookkeeping, leaves the fetches for the later steps behind them in flight)
+				if constexpr (WPS > 2) if (gl < nRec) { const uint4* rp0 = reinterpret_cast<const uint4*>(&recs(firstRec + gl)); rec0 = rp0[0]; rec1 = rp0[1]; rec2 = rp0[2]; }
+				rqp[0] = rqA;
+				if constexpr (kP > 1) if (nRec > (uint32_t)G && gl + G < nRec) rqp[kP - 1] = recs(firstRec + G + gl).rq;      // (a second pass: fetched here, off the first pass's chain)
 				if (!attempt)
 				{
 					dqC = make_uint4(0, 0, 0, 0); ppB = 0; rqB = 0;
-					if (pi + 2 <= nPos) dqC = *reinterpret_cast<const uint4*>(desc + pi + 2);
+					if (pi + 2 <= nPos) dqC = *reinterpret_cast<const uint4*>(&desc(pi + 2));
 					if (pi + 1 <= nPos)
 					{
-						if (gl < ((dqB.x >> 16) & 0xFFu)) ppB = posPrev[(dqB.x & 0xFFFFu) + gl];
-						if (gl < (dqB.z & 0xFFFFu)) rqB = recs[dqB.y + gl].rq;
-						if constexpr (WPS <= 2) if (gl < (dqB.z & 0xFFFFu)) { const uint4* rp0 = reinterpret_cast<const uint4*>(recs + dqB.y + gl); recB0 = rp0[0]; recB1 = rp0[1]; recB2 = rp0[2]; }
+						if (gl < ((dqB.x >> 16) & 0xFFu)) ppB = posPrev((dqB.x & 0xFFFFu) + gl);
+						if (gl < (dqB.z & 0xFFFFu)) rqB = recs(dqB.y + gl).rq;
+						if constexpr (WPS <= 2) if (gl < (dqB.z & 0xFFFFu)) { const uint4* rp0 = reinterpret_cast<const uint4*>(&recs(dqB.y + gl)); recB0 = rp0[0]; recB1 = rp0[1]; recB2 = rp0[2]; }
 					}
 				}
-				if constexpr (WPS > 2) if (gl < nRec) { const uint4* rp0 = reinterpret_cast<const uint4*>(recs + firstRec + gl); rec0 = rp0[0]; rec1 = rp0[1]; rec2 = rp0[2]; }
-				rqp[0] = rqA;
-				if constexpr (kP > 1) if (nRec > (uint32_t)G && gl + G < nRec) rqp[kP - 1] = recs[firstRec + G + gl].rq;      // (a second pass: fetched here, off the first pass's chain)
 				// ---- nodes of the position (lane j = node i0 + j): incoming state range and live count from the ring ----
 				uint32_t pBeg = 0, nP = 0, nLv = 0; bool bad = false; uint32_t why = 0;      // (nLv: the live ones among the nP incoming states)
 				if (gl < m)
@@ -460,6 +498,7 @@
 						if (ps_ * G + gl < nRec && (rq & PR_OUT_FIRST) && nPk >= 4) wantL |= 1u << nlR;
 					}
 					const uint32_t want = grpOr<G>(wantL);
+					const DevState* st = want ? stArena() : nullptr;
 					for (uint32_t wn = want; wn; wn &= wn - 1)
 					{
 						const uint32_t j = (uint32_t)__ffs((int)wn) - 1u;
@@ -517,21 +556,22 @@
 					if (gl < nRec) { ldsStore4(lds + PosLay::RECS + 48 * gl, rec0); ldsStore4(lds + PosLay::RECS + 48 * gl + 16, rec1); ldsStore4(lds + PosLay::RECS + 48 * gl + 32, rec2); }
 					if (gl == 0)
 					{
-						LDS_AS uint64_t* g64 = (LDS_AS uint64_t*)gctx;
-						g64[0] = (uint64_t)st; g64[1] = (uint64_t)(recs + firstRec); g64[2] = (uint64_t)uniq; g64[3] = (uint64_t)nodeTypo;
-						gctx[8] = stCap; gctx[9] = stTop; gctx[10] = stTop; gctx[11] = ringTop; gctx[12] = 0; gctx[13] = retry0 | (retry1 << 16);
+						gctx[8] = stCap; gctx[9] = stTop; gctx[10] = stTop; gctx[11] = ringTop; gctx[13] = retry0 | (retry1 << 16);
 #ifdef KAMD_CONG
 						gctx[14] = ofNodes;
 #else
 						gctx[14] = 0;
 #endif
-						gctx[15] = 0;
 						*ovfL = 0;
 					}
 					posStart = stTop;
 				}
 				PTL(1)
 			}
+			// (three waves per SIMD: a group that stages its records has waited for them, and with them for the fetches issued behind them.  A group that stopped
+			// above has not, and the head of the next step would wait there for everything in flight -- the state stores of this step among them -- before it
+			// may reuse the registers)
+			if constexpr (WPS > 2) POS_LOADS_ARRIVED();
 			__syncthreads();
 
 			for (uint32_t pass = 0; pass < kP; ++pass)
@@ -545,7 +585,7 @@
 					rinfo[gl] = pBegRp[kP - 1] | ((rqp[kP - 1] & 0xFFu) << 27);
 					if (G + gl < nRec)
 					{
-						const uint4* rp0 = reinterpret_cast<const uint4*>(recs + firstRec + G + gl);
+						const uint4* rp0 = reinterpret_cast<const uint4*>(&recs(firstRec + G + gl));
 						ldsStore4(lds + PosLay::RECS + 48 * gl, rp0[0]); ldsStore4(lds + PosLay::RECS + 48 * gl + 16, rp0[1]); ldsStore4(lds + PosLay::RECS + 48 * gl + 32, rp0[2]);
 					}
 				}
@@ -1012,7 +1052,7 @@
 						LDS_AS uint32_t* dwp = ldsPtr<uint32_t>(lds + PosLay::DWIN) + (((posStart + i) >> 5) & (PosLay::DWIN_WORDS - 1u));
 						if (kill) ldsOr(dwp, 1u << ((posStart + i) & 31u)); else ldsAnd(dwp, ~(1u << ((posStart + i) & 31u)));
 					}
-					if (kill) { st[posStart + i].dead = 1; if (ringTop - (posStart + i) <= PHR) ldsPtr<uint32_t>(hotR + 16 * ((posStart + i) & (PHR - 1)) + 12)[0] |= 1u << 16; }
+					if (kill) { stArena()[posStart + i].dead = 1; if (ringTop - (posStart + i) <= PHR) ldsPtr<uint32_t>(hotR + 16 * ((posStart + i) & (PHR - 1)) + 12)[0] |= 1u << 16; }
 					ldsAdd(&nCnt[(bits >> 8) & 0xFu], 1u | ((bits & PSB_PASS1) ? 0u : 1u << 8) | (kill ? 0u : 1u << 16) | ((kill || (bits & SB_STATE_SOCKET)) ? 0u : 1u << 24));
 				}
 				waveSyncLds();
@@ -1067,7 +1107,7 @@
 						for (uint32_t x = pi + 1; x <= nPos; x += G)
 						{
 							uint32_t st4 = 0; TYPO_ONLY(uint32_t st8 = 0;)
-							if (x + gl <= nPos) { st4 = posStarts[x + gl]; TYPO_ONLY(st8 = posStarts2[x + gl];) }
+							if (x + gl <= nPos) { st4 = posStarts(x + gl); TYPO_ONLY(st8 = W.posMask[nBase2 + x + gl];) }
 							const uint32_t nx = nPos - x + 1 < (uint32_t)G ? nPos - x + 1 : (uint32_t)G;
 							for (uint32_t t = 0; t < nx; ++t)
 							{
@@ -1099,11 +1139,11 @@
 				{
 					const uint32_t i = i0 + gl, ns = posStart + inclCnt - myCnt;
 					rBeg[i & (RING - 1)] = ns; rEnd[i & (RING - 1)] = ns + myCnt; rCum[i & (RING - 1)] = cumLive + inclLive;
-					nodeStOff[i] = ns; nodeStCnt[i] = myCnt; nodeLive[i] = (uint16_t)myLive;
+					nodeStOff(i) = ns; nodeStCnt(i) = myCnt; nodeLive(i) = (uint16_t)myLive;
 #ifdef KAMD_POS_TRACE
 					fprintf(stderr, "commit pi %u node %u ns %u cnt %u live %u free %u p0 %u attempt %u\n", pi, i, ns, myCnt, myLive, myFree, myP0, attempt);
 #endif
-					reach[i] = (uint8_t)((flagBits >> gl) & 1u);      // (a formless node's flag is never set by its own evaluation: it keeps what the last test left, PathEvaluator.hpp:1300-1318)
+					reach(i) = (uint8_t)((flagBits >> gl) & 1u);      // (a formless node's flag is never set by its own evaluation: it keeps what the last test left, PathEvaluator.hpp:1300-1318)
 				}
 				cumLive += GSHFL(inclLive, G - 1);
 				// next step: B becomes A
@@ -1117,16 +1157,18 @@
 			// end-candidate list k_finish_paths sorts and selects from, left in the unused tail of the chunk's state arena (what finishChunk does for
 			// the general kernel: written out here once more so that this kernel holds no function call) ----
 			{
-				const uint4 enq = reinterpret_cast<const uint4*>(W.nodes + nBase + (Gn - 1))[0];      // {form, start | end << 16, prev | sibling << 16, ...}
+				const uint32_t chunkE = gctx[12], Gn = gctx[15];
+				const uint4 enq = reinterpret_cast<const uint4*>(&W.nodes[nBase + Gn - 1])[0];      // {form, start | end << 16, prev | sibling << 16, ...}
 				const uint32_t enPrev = enq.z & 0xFFFFu, enNPrev = W.nodes[nBase + Gn - 1].nPrev;
 				const uint32_t firstPrev = Gn - 1 - enPrev;
-				const uint32_t pBegE = nodeStOff[firstPrev];
-				const uint32_t nPE = (enPrev && enNPrev) ? nodeStOff[firstPrev + enNPrev - 1] + nodeStCnt[firstPrev + enNPrev - 1] - pBegE : 0u;
+				const uint32_t pBegE = nodeStOff(firstPrev);
+				const uint32_t nPE = (enPrev && enNPrev) ? nodeStOff(firstPrev + enNPrev - 1) + nodeStCnt(firstPrev + enNPrev - 1) - pBegE : 0u;
+				DevState* st = stArena(); const uint8_t* uniq = uniqStates();
 				EndCand* endBuf = reinterpret_cast<EndCand*>(st + stTop);
 				const uint64_t freeBytes = (uint64_t)(stCap - stTop) * sizeof(DevState);
 				const uint32_t endCap = freeBytes > (uint64_t)Gn * 4 ? (uint32_t)((freeBytes - (uint64_t)Gn * 4) / sizeof(EndCand)) : 0u;
-				const bool openEnding = (B.chunkFlags[chunk] & 1) != 0;
-				const uint32_t nUniq = B.spOff[chunk + 1] - B.spOff[chunk];
+				const bool openEnding = (B.chunkFlags[chunkE] & 1) != 0;
+				const uint32_t nUniq = B.spOff[chunkE + 1] - B.spOff[chunkE];
 				uint32_t nEnd = 0; bool endOverflow = false;
 				for (uint32_t pb = 0; pb < nPE; pb += G)
 				{
@@ -1178,6 +1220,7 @@
 				const bool anyOverflow = GBALLOT(endOverflow) != 0;
 				if (gl == 0)
 				{
+					DevChunkResult* res = &W.results[chunkE];
 					res->nEnd = nEnd; res->endOff = stTop; res->nPaths = 0;
 					res->status = anyOverflow ? CS_ERR_STATE_OVERFLOW : CS_OK;
 					res->pad = kPosChunkDone;
@@ -1191,9 +1234,10 @@
 			__syncthreads();
 		}
 
+		const uint32_t chunkL = gctx[12], GnL = gctx[15];
 		// handing over after a test: the flags it left for the nodes not evaluated yet go to the table the general kernel reads
 		if (searching && stopAt && scanned)
-			for (uint32_t k = (stopAt & 0xFFFFFFu) + gl; k + 1 < Gn; k += G) reach[k] = (uint8_t)tbit(aLast, posPrev[k] >> 24);
+			for (uint32_t k = (stopAt & 0xFFFFFFu) + gl; k + 1 < GnL; k += G) reach(k) = (uint8_t)tbit(aLast, posPrev(k) >> 24);
 		PBEACON(11, stopAt, 0, 0)
 #ifdef KAMD_POS_DEBUG
 		PTL(11)
@@ -1221,7 +1265,7 @@
 				__syncthreads();
 				LDS_AS uint32_t* lst = ldsPtr<uint32_t>(PosLay::ROWMAP);      // (behind the general search's own layout: Lay<16>::TOTAL <= ROWMAP is asserted below)
 				static_assert(Lay<16>::TOTAL <= PosLayT<8>::ROWMAP && 3 * 4 * (64 / 8) <= 128, "list of the chunks carried on");
-				if (cont && gl == 0) { const uint32_t at = (uint32_t)__popcll(cm & lowerMask64); lst[3 * at] = chunk; lst[3 * at + 1] = stopAt; lst[3 * at + 2] = slot; }
+				if (cont && gl == 0) { const uint32_t at = (uint32_t)__popcll(cm & lowerMask64); lst[3 * at] = chunkL; lst[3 * at + 1] = stopAt; lst[3 * at + 2] = slot; }
 				const uint32_t nH = (uint32_t)__popcll(cm);
 				LDS_AS float* lb = ldsPtr<float>(Lay<16>::LB);
 				for (uint32_t t = lane; t < 2 * T_MAX + 1; t += 64)
@@ -1244,25 +1288,21 @@
 						const uint32_t chunkE = lst[3 * e], stopE = lst[3 * e + 1], slotE = lst[3 * e + 2];
 #ifdef KAMD_HIPEMU
 						const PosKernArgs A{ M, B, W, P, chunkOrder, nWork TYPO_ONLY(, nodeTypoAll) CONG_ONLY(, CGv) };
-						const bool ok = continueChunk(&A, chunkE, il, irow, slotE, stopE & 0xFFFFFFu, W.posScratch, chunkOrder, nWork);
+						continueChunk(&A, chunkE, il, irow, slotE, stopE, W.posScratch, chunkOrder, nWork);
 #else
-						const bool ok = continueChunk(chunkE, il, irow, slotE, stopE & 0xFFFFFFu, W.posScratch, chunkOrder, nWork);
+						continueChunk(chunkE, il, irow, slotE, stopE, W.posScratch, chunkOrder, nWork);
 #endif
-						if (il == 0)
-						{
-							if (ok) W.results[chunkE].pad = kPosChunkDone | (stopE & 0xFF000000u);
-							else { W.results[chunkE].pad = stopE; *W.posHandOver = 1; }
-						}
 					}
 				}
 #ifdef KAMD_HIPEMU
 				hipemu_set_width(8);
 #endif
 			}
-			if (handOver && !cont && gl == 0) { res->pad = stopAt; *W.posHandOver = 1; }
+			if (handOver && !cont && gl == 0) { W.results[chunkL].pad = stopAt; *W.posHandOver = 1; }
 		}
 		else
 		{
+		if (handOver && !cont && gl == 0) { W.results[chunkL].pad = stopAt; *W.posHandOver = 1; }
 		if (WBALLOT(cont))
 		{
 			__syncthreads();
@@ -1281,15 +1321,14 @@
 			{
 #ifdef KAMD_HIPEMU
 				const PosKernArgs A{ M, B, W, P, chunkOrder, nWork TYPO_ONLY(, nodeTypoAll) CONG_ONLY(, CGv) };
-				cont = continueChunk(&A, chunk, gl, grp, slot, stopAt & 0xFFFFFFu, W.posScratch, chunkOrder, nWork);
+				continueChunk(&A, chunkL, gl, grp, slot, stopAt, W.posScratch, chunkOrder, nWork);
 #else
-				cont = continueChunk(chunk, gl, grp, slot, stopAt & 0xFFFFFFu, W.posScratch, chunkOrder, nWork);
+				continueChunk(chunkL, gl, grp, slot, stopAt, W.posScratch, chunkOrder, nWork);
 #endif
-				if (cont && gl == 0) res->pad = kPosChunkDone | (stopAt & 0xFF000000u);      // (bits 24..31: why it left the position steps, developer statistics)
 			}
 		}
-		if (handOver && !cont && gl == 0) { res->pad = stopAt; *W.posHandOver = 1; }
 		}
+#undef POS_LOADS_ARRIVED
 #undef GBALLOT
 #undef GSHFL
 #undef WBALLOT
