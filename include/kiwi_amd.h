@@ -96,6 +96,11 @@ kamd_results_h kamd_res_merge_strided(const uint8_t* const* parts, const size_t*
 int kamd_debug_exact_math(const float* x, float* exp_out, float* log_out, uint32_t n);
 /* developer probe: tanh_out[i] = tanhf of x[i] computed ON THE DEVICE by csrc/exact_math.hpp (bit-identical to glibc 2.35; the frequency-based unknown-form scores use it) */
 int kamd_debug_exact_tanh(const float* x, float* tanh_out, uint32_t n);
+/* developer probe: the wave-wide scans of csrc/wave_scan.hpp run ON THE DEVICE, one wavefront per case of 64 lanes (arrays of 64 * n_cases words, lane-major inside a case):
+ * sum_out = inclusive sum of x; seg_sum_out = inclusive sum of x inside segments; (seg_or_lo_out, seg_or_hi_out) = inclusive OR of the 64-bit value (or_lo, or_hi) inside
+ * segments; last_out[case] = the sum's wave total.  start[lane] = the first lane of the lane's segment (<= lane, equal over a segment) */
+int kamd_debug_wave_scan(const uint32_t* x, const uint32_t* start, const uint32_t* or_lo, const uint32_t* or_hi, uint32_t* sum_out, uint32_t* seg_sum_out, uint32_t* seg_or_lo_out, uint32_t* seg_or_hi_out,
+	uint32_t* last_out, uint32_t n_cases);
 /* developer probe: the GLOBAL CoNgram model's score (reference CoNgramModel::progress / progressMatrix*, src/CoNgramModel.cpp:802-868, 1037-1466; csrc/cong_global.hpp)
  * of next[i] after context id ctx[i] with the seven history words hist7[7 * i ..], computed ON THE DEVICE; flags[i] bit 0 = the progressMatrix* entry, bit 1 = output
  * scale first.  The model must carry the window sections (cong.mdl windowSize 7).  The search does not use this model type yet (kiwi_init refuses CONG_GLOBAL). */

@@ -20,6 +20,7 @@ static_assert(sizeof(kamd_token_t) == sizeof(FlatToken) && offsetof(kamd_token_t
 	"kamd_token_t is the layout of kamd::FlatToken");
 
 namespace kamd { void exactMathProbe(const float* x, float* e, float* l, float* t, uint32_t n); }
+namespace kamd { void waveScanProbe(const uint32_t* x, const uint32_t* start, const uint32_t* lo, const uint32_t* hi, uint32_t* sum, uint32_t* seg, uint32_t* orLo, uint32_t* orHi, uint32_t* last, uint32_t nCases); }
 namespace kamd { void conggProbe(const FlatModel& m, const uint32_t* ctx, const uint32_t* hist, const uint32_t* next, const uint8_t* flags, float* out, uint32_t n); }
 
 namespace
@@ -287,6 +288,12 @@ extern "C"
 	int kamd_debug_exact_tanh(const float* x, float* tanh_out, uint32_t n)
 	{
 		return guarded([&]() { kamd::exactMathProbe(x, nullptr, nullptr, tanh_out, n); return 0; }, -1);
+	}
+
+	int kamd_debug_wave_scan(const uint32_t* x, const uint32_t* start, const uint32_t* or_lo, const uint32_t* or_hi, uint32_t* sum_out, uint32_t* seg_sum_out, uint32_t* seg_or_lo_out, uint32_t* seg_or_hi_out,
+		uint32_t* last_out, uint32_t n_cases)
+	{
+		return guarded([&]() { kamd::waveScanProbe(x, start, or_lo, or_hi, sum_out, seg_sum_out, seg_or_lo_out, seg_or_hi_out, last_out, n_cases); return 0; }, -1);
 	}
 
 	int kamd_debug_cong_global(kamd_engine_h h, const uint32_t* ctx, const uint32_t* hist7, const uint32_t* next, const uint8_t* flags, float* out, uint32_t n)

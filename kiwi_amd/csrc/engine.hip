@@ -27,6 +27,7 @@
 #include "typo_lattice_kernel.hpp"
 #include "typo_graph_kernel.hpp"
 #include "cong_query_kernel.hpp"
+#include "wave_scan.hpp"
 
 namespace kamd
 {
@@ -35,6 +36,7 @@ namespace kamd
 	__global__ void k_build_lattice_big(ModelView M, BatchView B, WorkView W, SearchParams P, uint32_t chunkBegin, uint32_t chunkCount, uint32_t ldsBytes, uint32_t waveLayout);
 	__global__ void k_lattice_wave(ModelView M, BatchView B, WorkView W, SearchParams P, const uint32_t* chunkList, uint32_t chunkCount, uint32_t ldsBytes, uint32_t matchRatio16, uint32_t expandMode);
 	__global__ void k_expand_cands(ModelView M, BatchView B, WorkView W, uint32_t chunkBegin, uint32_t chunkCount, uint32_t transposedOrder, const uint8_t* distMask);
+	__global__ void k_fill_cand_rows(ModelView M, CandStatic* rows, uint32_t nForms, uint32_t nCand, uint32_t transposedOrder);
 	__global__ void k_expand_pos(ModelView M, BatchView B, WorkView W, SearchParams P, uint32_t chunkBegin, uint32_t chunkCount, const float* nodeTypoAll, uint32_t useChr);
 	__global__ void k_unk_chr(ModelView M, BatchView B, WorkView W, ChrView C, uint32_t chunkBegin, uint32_t chunkCount, uint32_t hiTok, uint32_t loTok);
 	__global__ void k_unk_chr_freq(ModelView M, BatchView B, WorkView W, ChrView C, ChrFreqParams Q, float chrBias, uint32_t chunkBegin, uint32_t chunkCount, uint32_t hiTok, uint32_t loTok);
@@ -265,6 +267,7 @@ namespace kamd
 		int device = 0;
 		uint32_t persistBlocks = 0;
 		int latticeGroupForced = 0;      // KAMD_LATTICE_GROUP=16 / 64: lanes per chunk of k_build_lattice
+		bool latticeExpand = true;       // k_lattice_wave also writes the candidate records and the position program; KAMD_LATTICE_EXPAND=0 (read when the engine opens): k_expand_cands / k_expand_pos do
 		bool latticeWave = true;         // k_lattice_wave (all lanes build the lattice); KAMD_LATTICE_WAVE=0: k_build_lattice's one-lane replay
 		// LDS room of k_lattice_wave for packed matches, sixteenths per text unit: follows what the model's dictionary produced in the batches so far
 		// (read back with every batch's counters); the first batch assumes 3 per unit, a chunk beyond the room goes to the wide launch (KAMD_LATTICE_RATIO fixes it)
@@ -427,6 +430,18 @@ namespace kamd
 		}
 		else { v.lmHash = impl->up(m.lmHash); v.lmHashMask = m.lmHashMask; v.lmRoot2 = impl->up(m.lmRoot2); v.lmBackoff = impl->up(m.lmBackoff); }
 		v.lmHtxNode = (m.congDim || m.lmHtxNode.empty()) ? nullptr : impl->up(m.lmHtxNode);      // history-transformed Knlm only
+		{
+			// the candidate rows of the model's own forms (ModelView::candRows, 48 bytes per entry of formCand), made on the device from the tables just uploaded
+			impl->modelBufs.emplace_back(new DevBuf);
+			DevBuf& rows = *impl->modelBufs.back();
+			const uint32_t nForms = (uint32_t)m.forms.size(), nCand = (uint32_t)m.formCand.size();
+			rows.ensure(std::max<size_t>((size_t)nCand * sizeof(CandStatic), 16));
+			HIPCHECK(hipMemsetAsync(rows.p, 0, (size_t)nCand * sizeof(CandStatic), impl->stream));
+			if (nForms) hipLaunchKernelGGL(k_fill_cand_rows, dim3((nForms + 255) / 256), dim3(256), 0, impl->stream, v, rows.as<CandStatic>(), nForms, nCand, impl->hasCong ? 1u : 0u);
+			HIPCHECK(hipGetLastError());
+			HIPCHECK(hipStreamSynchronize(impl->stream));
+			v.candRows = rows.p;
+		}
 		// (dialect bits: the room behind them is zero -- a temporary entry belongs to no dialect)
 		v.formDialect = nullptr;      // (a bake-time fact: flat_model.hpp ModelView::formDialect)
 		v.morphDialect = m.morphDialect.empty() ? nullptr : impl->up(m.morphDialect, I_::kTempMorphs);
@@ -476,6 +491,7 @@ namespace kamd
 		if (const char* pc = std::getenv("KAMD_POS_CONT")) impl->posContSlots = (uint32_t)std::max(0, std::min(4096, std::atoi(pc)));
 		if (const char* lg = std::getenv("KAMD_LATTICE_GROUP")) { const int v = std::atoi(lg); if (v == 16 || v == 64) impl->latticeGroupForced = v; }
 		if (const char* lw = std::getenv("KAMD_LATTICE_WAVE")) impl->latticeWave = std::atoi(lw) != 0;
+		if (const char* le = std::getenv("KAMD_LATTICE_EXPAND")) impl->latticeExpand = std::atoi(le) != 0;
 		if (const char* ss = std::getenv("KAMD_STATE_SCALE")) { impl->stateScale64[0] = impl->stateScale64[1] = (uint32_t)std::min(64, std::max(1, std::atoi(ss))); impl->stateScaleForced = true; }      // (64ths of the worst case)
 		if (const char* ps = std::getenv("KAMD_STATE_POOL")) { impl->poolFrac64 = (uint32_t)std::min(4096, std::max(0, std::atoi(ps))); impl->poolForced = true; }      // (64ths of the arenas' total; 0: no pool)
 		if (const char* lr = std::getenv("KAMD_LATTICE_RATIO")) { impl->latticeRatio16 = (uint32_t)std::min(4096, std::max(4, std::atoi(lr))); impl->latticeRatioForced = true; }
@@ -908,6 +924,35 @@ namespace kamd
 		if (t) HIPCHECK(hipMemcpy(t, dt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
 	}
 
+	// Probe of csrc/wave_scan.hpp on the device (tests/test_gpu_wave_scan.py): one wavefront per case of 64 lanes, all lanes active.  sum = waveInclSum(x),
+	// seg = waveSegInclSum(x, start), (orLo, orHi) = waveSegInclOr(lo, hi, start), last[case] = waveLast(sum)
+	__global__ void __launch_bounds__(64) k_wave_scan_probe(const uint32_t* x, const uint32_t* start, const uint32_t* lo, const uint32_t* hi, uint32_t* sum, uint32_t* seg, uint32_t* orLo, uint32_t* orHi, uint32_t* last)
+	{
+		const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+		const uint32_t s = waveInclSum(x[i]);
+		sum[i] = s;
+		seg[i] = waveSegInclSum(x[i], start[i]);
+		uint32_t l = lo[i], h = hi[i];
+		waveSegInclOr(l, h, start[i]);
+		orLo[i] = l; orHi[i] = h;
+		const uint32_t tot = waveLast(s);
+		if (threadIdx.x == 0) last[blockIdx.x] = tot;
+	}
+	void waveScanProbe(const uint32_t* x, const uint32_t* start, const uint32_t* lo, const uint32_t* hi, uint32_t* sum, uint32_t* seg, uint32_t* orLo, uint32_t* orHi, uint32_t* last, uint32_t nCases)
+	{
+		if (!nCases) return;
+		const size_t bytes = (size_t)nCases * 64 * 4;
+		DevBuf in[4], out[4], dLast;
+		const uint32_t* src[4] = { x, start, lo, hi }; uint32_t* dst[4] = { sum, seg, orLo, orHi };
+		for (int k = 0; k < 4; ++k) { in[k].ensure(bytes); out[k].ensure(bytes); HIPCHECK(hipMemcpy(in[k].p, src[k], bytes, hipMemcpyHostToDevice)); }
+		dLast.ensure((size_t)nCases * 4 + 16);
+		hipLaunchKernelGGL(k_wave_scan_probe, dim3(nCases), dim3(64), 0, 0, in[0].as<uint32_t>(), in[1].as<uint32_t>(), in[2].as<uint32_t>(), in[3].as<uint32_t>(),
+			out[0].as<uint32_t>(), out[1].as<uint32_t>(), out[2].as<uint32_t>(), out[3].as<uint32_t>(), dLast.as<uint32_t>());
+		HIPCHECK(hipGetLastError());
+		for (int k = 0; k < 4; ++k) HIPCHECK(hipMemcpy(dst[k], out[k].p, bytes, hipMemcpyDeviceToHost));
+		HIPCHECK(hipMemcpy(last, dLast.p, (size_t)nCases * 4, hipMemcpyDeviceToHost));
+	}
+
 	// Probe of csrc/cong_global.hpp on the device (tests/test_cong_global.py): the score of `next[i]` after context ctx[i] and the seven history words hist[i][0..6]
 	// under the GLOBAL CoNgram model -- flags[i] bit 0: the progressMatrix* entry instead of state.next(), bit 1: output scale first -- and the local score for a
 	// word that is no valid distant token.  The first device piece of that model type (the search kernel does not use it yet): the arithmetic and the layout of
@@ -1159,7 +1204,7 @@ namespace kamd
 				// the candidate records and the position program written by the lattice kernel itself (no k_expand_cands / k_expand_pos pass over these chunks):
 				// for the position-step search without a blocklist and without character-model scores of unknown forms (k_unk_chr sits between the two);
 				// bit 1: a CoNgram model (records in the transposed evaluator's order).  KAMD_LATTICE_EXPAND=0: the two kernels do it
-				static const bool fuseExpand = !(getenv("KAMD_LATTICE_EXPAND") && std::atoi(getenv("KAMD_LATTICE_EXPAND")) == 0);
+				const bool fuseExpand = I.latticeExpand;
 				const bool posEarly = b.wv.posRecs && sp.topN == 1 && !I.groupLanesForced && S <= 8 && (!b.typo.typo || I.posPathTypo);
 				const uint32_t expandMode = (fuseExpand && posEarly && !b.wv.unkChr && !b.wv.blockBits) ? (1u | (I.hasCong ? 2u : 0u)) : 0u;
 				if (getenv("KAMD_LATTICE_PROFILE")) { lwProf.ensure((size_t)nC * 64); HIPCHECK(hipMemsetAsync(lwProf.p, 0, (size_t)nC * 64, sA)); b.wv.beacon = lwProf.as<uint32_t>(); }
@@ -1450,12 +1495,12 @@ namespace kamd
 			// developer aid (make lwprof): cycles per phase of k_lattice_wave, per wavefront
 			std::vector<uint32_t> rec((size_t)nC * 16);
 			HIPCHECK(hipMemcpy(rec.data(), lwProf.p, rec.size() * 4, hipMemcpyDeviceToHost));
-			double pr[13] = {}; uint32_t seen = 0;
-			for (uint32_t c = 0; c < nC; ++c) { if (!rec[(size_t)c * 16]) continue; ++seen; for (int k2 = 0; k2 < 13; ++k2) pr[k2] += rec[(size_t)c * 16 + k2]; }
-			static const char* names[13] = { "stage", "type pass", "match ops", "groups", "clear", "by-time", "by-start", "publish", "checks", "ranks", "sweep+prefix", "emit", "pack offsets" };
-			double tot = 0; for (int k2 = 0; k2 < 13; ++k2) tot += pr[k2];
+			double pr[15] = {}; uint32_t seen = 0;
+			for (uint32_t c = 0; c < nC; ++c) { if (!rec[(size_t)c * 16]) continue; ++seen; for (int k2 = 0; k2 < 15; ++k2) pr[k2] += rec[(size_t)c * 16 + k2]; }
+			static const char* names[15] = { "stage", "type pass", "match ops", "groups", "clear", "by-time", "by-start", "publish", "checks", "ranks", "sweep+prefix", "candidate counts", "pack offsets + candidate rows", "position table", "nodes + records" };
+			double tot = 0; for (int k2 = 0; k2 < 15; ++k2) tot += pr[k2];
 			fprintf(stderr, "[lattice profile] clock ticks per wavefront (%u chunks):", seen);
-			for (int k2 = 0; k2 < 13; ++k2) fprintf(stderr, " %s %.0f (%.0f%%);", names[k2], seen ? pr[k2] / seen : 0.0, tot ? 100.0 * pr[k2] / tot : 0.0);
+			for (int k2 = 0; k2 < 15; ++k2) fprintf(stderr, " %s %.0f (%.0f%%);", names[k2], seen ? pr[k2] / seen : 0.0, tot ? 100.0 * pr[k2] / tot : 0.0);
 			fprintf(stderr, " total %.0f\n", seen ? tot / seen : 0.0);
 		}
 		if (getenv("KAMD_LATTICE_STATS"))
@@ -1468,8 +1513,8 @@ namespace kamd
 			uint32_t nEx = 0, nProg = 0;
 			for (uint32_t c = 0; c < nC; ++c) if (ex[c]) { ++nEx; if (b.wv.posDesc) { PosDesc d; HIPCHECK(hipMemcpy(&d, b.wv.posDesc + b.nodeBase[c], sizeof(d), hipMemcpyDeviceToHost)); nProg += d.firstRec != 0; } }
 			fprintf(stderr, "[lattice wave] records written by the lattice kernel: %u chunks (%u with a position program)\n", nEx, nProg);
-			fprintf(stderr, "[lattice wave] chunks %u: built %u (%.2f rounds each); handed over: matches %u, ops %u, long span / rounds %u, no end node %u, long node %u, no start %u; ops per text unit: mean %.2f, max %.2f (matches: max %.2f)\n",
-				(uint32_t)nC, c16[10], c16[10] ? (double)c16[11] / c16[10] : 0.0, c16[4], c16[5], c16[6], c16[7], c16[8], c16[9], c16[15] ? (double)c16[14] / c16[15] : 0.0, c16[12] / 100.0, c16[13] / 100.0);
+			fprintf(stderr, "[lattice wave] chunks %u: built %u (%.2f rounds each); handed over: matches %u, ops %u, long span / rounds %u, no end node %u, long node %u, no start %u; ops per text unit: mean %.2f, max %.2f (matches: max %.2f); ops %u in %u text units\n",
+				(uint32_t)nC, c16[10], c16[10] ? (double)c16[11] / c16[10] : 0.0, c16[4], c16[5], c16[6], c16[7], c16[8], c16[9], c16[15] ? (double)c16[14] / c16[15] : 0.0, c16[12] / 100.0, c16[13] / 100.0, c16[14], c16[15]);
 		}
 		if (b.wv.posRecs && getenv("KAMD_POS_STATS"))
 		{

@@ -150,6 +150,10 @@ namespace kamd
 		const LmRootRec* lmRoot2;     // [vocab]
 		const LmBackoff* lmBackoff;   // [nLmNodes]
 		const void* unkPacks;         // device only: CandStatic[2] for the unknown-noun candidates NNG, NNP (PathEvaluator.hpp:1204-1206)
+		// device only: one CandStatic per entry of the model's own formCand[], at the same index (candStaticOf of that candidate; CoNgram engines: the rows of
+		// a form in the transposed evaluator's class order).  Filled once when the model is uploaded (k_fill_cand_rows); the batch-local entries a
+		// pretokenized batch puts behind formCand[] have no rows.  Read by k_lattice_wave only
+		const void* candRows;
 		// history-transformed Knlm (KnLangModelHeader::htx_offset; the reference's builder writes one by default): per word the root's child for its
 		// TRANSFORMED id (a node index, 0 = none) -- where a walk lands when no context continues with the word (Knlm.cpp:61-70, 116-126); null = plain model
 		const int32_t* lmHtxNode;
@@ -477,7 +481,7 @@ namespace kamd
 			v.lmHtxNode = lmHtxNode.empty() ? nullptr : lmHtxNode.data();
 			v.formUnkChr = formUnkChr.empty() ? nullptr : formUnkChr.data();
 			v.formChrTok = formChrTok.empty() ? nullptr : formChrTok.data();
-			v.lmChain = nullptr;
+			v.lmChain = nullptr; v.unkPacks = nullptr; v.candRows = nullptr;
 			v.trieEdges = trieEdges.empty() ? nullptr : trieEdges.data(); v.trieEdgeMask = trieEdgeMask;
 			v.formDialect = formDialect.empty() ? nullptr : formDialect.data(); v.morphDialect = morphDialect.empty() ? nullptr : morphDialect.data();
 			return v;

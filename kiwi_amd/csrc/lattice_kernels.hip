@@ -888,6 +888,31 @@ namespace kamd
 		}
 	}
 
+	// ModelView::candRows: the static record of every candidate of every form of the model, once per engine when the model is uploaded (one thread per
+	// form).  rows[candOff + i] = candStaticOf of the form's i-th candidate -- in dictionary order, or (transposedOrder, CoNgram engines) in the class order
+	// of k_expand_cands above without a distant-token mask, each class in dictionary order: what k_lattice_wave copies into a node's packs
+	__global__ void __launch_bounds__(256) k_fill_cand_rows(ModelView M, CandStatic* rows, uint32_t nForms, uint32_t nCand, uint32_t transposedOrder)
+	{
+		const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+		if (f >= nForms) return;
+		const FormRec fr = M.forms[f];
+		const uint32_t candOff = fr.candOff, candCnt = fr.candCnt;
+		if (candOff > nCand || candCnt > nCand - candOff) return;
+		uint32_t classAt[5] = { 0, 0, 0, 0, 0 };
+		if (transposedOrder)
+		{
+			uint32_t classCnt[5] = { 0, 0, 0, 0, 0 };
+			for (uint32_t k = 0; k < candCnt; ++k) { const MorphRec r = M.morphs[M.formCand[candOff + k]]; ++classCnt[candClassOf(r.tag, r.socket, r.flags)]; }
+			for (uint32_t c = 1; c < 5; ++c) classAt[c] = classAt[c - 1] + classCnt[c - 1];
+		}
+		for (uint32_t k = 0; k < candCnt; ++k)
+		{
+			const CandStatic o = candStaticOf(M, M.formCand[candOff + k]);
+			const uint32_t at = transposedOrder ? classAt[candClassOf((uint8_t)o.m1.z, o.m1.z >> 24, o.m1.y & 0xFFFF)]++ : k;
+			rows[candOff + at] = o;
+		}
+	}
+
 	// ------------------------------------------------------------------------------------------------
 	// Position program of the position-step search kernel (k_pos_path, viterbi_pos.inc; device_types.hpp PosRec / PosDesc).
 	// The search sweeps the lattice one END POSITION at a time; what a step does is, apart from the incoming paths, a function of the lattice:

@@ -30,6 +30,7 @@
 #include "device_types.hpp"
 #include "feature.hpp"
 #include "lattice_expand.hpp"
+#include "wave_scan.hpp"
 
 namespace kamd
 {
@@ -54,8 +55,8 @@ namespace kamd
 
 	// LW_PROFILE build (make lwprof): cycles per phase, one record of 16 words per chunk in WorkView::beacon
 #ifdef LW_PROFILE
-#define LW_T0() unsigned long long lwT = clock64(); uint32_t lwAcc[13] = {};
-#define LW_MARK(k) { const unsigned long long lwN = clock64(); lwAcc[(k)] += (uint32_t)(lwN - lwT); lwT = lwN; if ((k) == 12 && lane == 0 && W.beacon) for (int lwI = 0; lwI < 13; ++lwI) W.beacon[16 * (size_t)chunk + lwI] = lwAcc[lwI]; }
+#define LW_T0() unsigned long long lwT = clock64(); uint32_t lwAcc[15] = {};
+#define LW_MARK(k) { const unsigned long long lwN = clock64(); lwAcc[(k)] += (uint32_t)(lwN - lwT); lwT = lwN; if ((k) == 14 && lane == 0 && W.beacon) for (int lwI = 0; lwI < 15; ++lwI) W.beacon[16 * (size_t)chunk + lwI] = lwAcc[lwI]; }
 #else
 #define LW_T0()
 #define LW_MARK(k)
@@ -129,10 +130,9 @@ namespace kamd
 			{
 				const uint32_t i = b0 + lane;
 				const uint32_t g = (i > 0 && i < nNs && nsToPos[i] - nsToPos[i - 1] > 1) ? 1u : 0u;
-				uint32_t incl = g;
-				for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+				const uint32_t incl = waveInclSum(g);
 				if (i < nNs) gapPre[i] = (uint16_t)(run + incl);
-				run += __shfl(incl, 63);
+				run += waveLast(incl);
 			}
 		}
 		waveSync();
@@ -204,10 +204,9 @@ namespace kamd
 				}
 				const uint32_t nMiscMine = (spec ? 1u : 0u) + (isS ? 1u : 0u) + (zsel ? 1u : 0u);
 				const uint32_t nOpsMine = nMiscMine + (flush ? (uint32_t)__popcll(mask[pj1]) : 0u);
-				uint32_t inclT = nOpsMine, inclM = nMiscMine;
-				for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(inclT, d), w = __shfl_up(inclM, d); if (lane >= d) { inclT += v; inclM += w; } }
+				const uint32_t inclT = waveInclSum(nOpsMine), inclM = waveInclSum(nMiscMine);
 				uint32_t T = Tbase + inclT - nOpsMine, mi = miscBase + inclM - nMiscMine;
-				const uint32_t totT = __shfl(inclT, 63), totM = __shfl(inclM, 63);
+				const uint32_t totT = waveLast(inclT), totM = waveLast(inclM);
 				if (Tbase + totT >= lay.opCap || miscBase + totM >= lay.miscCap) over = true;      // (uniform)
 				if (!over)
 				{
@@ -231,7 +230,7 @@ namespace kamd
 					}
 				}
 				Tbase += totT; miscBase += totM;
-				tC = __shfl(t, 63); sC = __shfl(sc, 63); ssC = __shfl(ss, 63); bC = __shfl(bb, 63); uC = __shfl(uu, 63);
+				tC = waveLast(t); sC = waveLast(sc); ssC = waveLast(ss); bC = waveLast(bb); uC = waveLast(uu);
 				if (b0 + 64 > n) { const uint32_t last = (n - 1) & 63u; tC = __shfl(t, last); sC = __shfl(sc, last); }      // (the running values beyond the text repeat the last unit's: no events there)
 			}
 			over = __ballot(over) != 0;
@@ -426,11 +425,10 @@ namespace kamd
 			{
 				const uint32_t q = b0 + lane;
 				const uint32_t c = q <= nPosAll ? grpOff[q] : 0u;
-				uint32_t incl = c;
-				for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+				const uint32_t incl = waveInclSum(c);
 				if (q <= nPosAll) grpOff[q] = run + incl;      // grpOff[q + 1] held the count of q: inclusive sum = first slot of position q
 				if (q < nPosAll) posA[q] = 0;                   // (scatter cursors)
-				run += __shfl(incl, 63);
+				run += waveLast(incl);
 			}
 		}
 		waveSync();
@@ -547,11 +545,7 @@ namespace kamd
 					const uint64_t mineSeg = sb & (((1ull << lane) - 1ull) | (1ull << lane));
 					const uint32_t start = mineSeg ? topBit(mineSeg) : 0u;      // first lane of this lane's segment (0: it began in an earlier block)
 					uint32_t lo = (uint32_t)contrib, hi = (uint32_t)(contrib >> 32);
-					for (uint32_t d = 1; d < 64; d <<= 1)
-					{
-						const uint32_t vl = __shfl_up(lo, d), vh = __shfl_up(hi, d);
-						if (lane >= d && lane - d >= start) { lo |= vl; hi |= vh; }
-					}
+					waveSegInclOr(lo, hi, start);
 					const uint32_t exLo = __shfl_up(lo, 1), exHi = __shfl_up(hi, 1);
 					uint64_t F = Fdict;
 					if (lane > start) F |= ((uint64_t)exHi << 32) | exLo;
@@ -588,8 +582,7 @@ namespace kamd
 						}
 					}
 					// rank of its nodes among the position's unknown-form nodes: segmented exclusive sum
-					uint32_t incl = own;
-					for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d && lane - d >= start) incl += v; }
+					const uint32_t incl = waveSegInclSum(own, start);
 					uint32_t rank = incl - own;
 					if (!mineSeg) rank += carryCnt;
 					if (act)
@@ -609,7 +602,7 @@ namespace kamd
 					if (segEnd) { cntU[q] = (uint16_t)(rank + own); if (rank + own == 0) base[q] = 0xFFFF; }
 					// carry into the next block: the segment of lane 63
 					const uint64_t fullF = ((uint64_t)hi << 32) | lo;
-					const uint32_t cLo = __shfl((uint32_t)fullF, 63), cHi = __shfl((uint32_t)(fullF >> 32), 63), cCnt = __shfl(rank + own, 63), cQ = __shfl(q, 63);
+					const uint32_t cLo = waveLast((uint32_t)fullF), cHi = waveLast((uint32_t)(fullF >> 32)), cCnt = waveLast(rank + own), cQ = waveLast(q);
 					const bool contSeg = sb == 0;      // no segment began in this block: lane 63 still continues the carried one
 					carryF = (contSeg ? carryF : 0ull) | ((uint64_t)cHi << 32) | cLo;
 					carryCnt = cCnt;      // (rank + own already includes the carried count when the segment continued)
@@ -671,7 +664,7 @@ namespace kamd
 					atomicAdd(&cntA[e], 1u);
 				}
 				// carry: the segment of the last lane
-				const uint32_t eLast = __shfl(e, 63);
+				const uint32_t eLast = waveLast(e);
 				const uint32_t startLast = sb ? topBit(sb) : 0u;
 				const uint32_t inLast = (uint32_t)__popcll(am & ~((1ull << startLast) - 1ull));
 				carryCnt = sb ? inLast : carryCnt + inLast;
@@ -731,10 +724,9 @@ namespace kamd
 			const uint32_t q = b0 + lane;
 			uint32_t c = 0;
 			if (q < nPosAll && keep[q]) c = q == 0 ? 1u : cntA[q] + cntU[q];
-			uint32_t incl = c;
-			for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+			const uint32_t incl = waveInclSum(c);
 			if (q < nPosAll) base[q] = (uint16_t)(nConn + incl - c);
-			nConn += __shfl(incl, 63);
+			nConn += waveLast(incl);
 		}
 		if (nConn + 1 >= cap) { if (lane == 0) W.results[chunk].status = CS_ERR_NODE_OVERFLOW; return; }
 		if (nConn > lay.nodeCap) LW_HAND_OVER(6)
@@ -769,10 +761,9 @@ namespace kamd
 		{
 			const uint32_t i = b0 + lane;
 			const uint32_t c = i < nConn ? cc[i] : 0u;
-			uint32_t incl = c;
-			for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+			const uint32_t incl = waveInclSum(c);
 			if (i < nConn) cc[i] = packTop + incl - c;
-			packTop += __shfl(incl, 63);
+			packTop += waveLast(incl);
 		}
 		waveSync();
 		// (uniform) the candidate records would not fit the chunk's pack region: report the overflow BEFORE anything of phase 8 is written -- the expansion
@@ -791,6 +782,7 @@ namespace kamd
 		const uint32_t nUniq = B.spOff[chunk + 1] - B.spOff[chunk];
 		CandStatic* packs = W.packs + W.packBase[chunk];
 		const CandStatic* unkPacks = reinterpret_cast<const CandStatic*>(M.unkPacks);
+		const CandStatic* candRows = reinterpret_cast<const CandStatic*>(M.candRows);
 		PosRec* recs = doExpand ? W.posRecs + W.packBase[chunk] : nullptr;
 		PosDesc* desc = doExpand ? W.posDesc + nBase : nullptr;
 		uint32_t* posSlow = grpOff; uint32_t* posPass1 = posA; uint32_t* posIdx = posZ;      // (free since the fixpoint ended)
@@ -835,17 +827,14 @@ namespace kamd
 					if (form == NOFORM) { recOff[ni] = 2; continue; }
 					const uint32_t candCnt = fc & 0x7FFFu, candOff = M.forms[form].candOff, pk = cc[ni];
 					const bool spaceBefore = spaceBeforeOf(nb, false);
-					uint32_t cnt = 0, classCnt[5] = { 0, 0, 0, 0, 0 };
-					if (transposed)
-						for (uint32_t k = 0; k < candCnt; ++k) { const MorphRec r = M.morphs[M.formCand[candOff + k]]; ++classCnt[candClassOf(r.tag, r.socket, r.flags)]; }
-					uint32_t classAt[5] = { 0, classCnt[0], classCnt[0] + classCnt[1], classCnt[0] + classCnt[1] + classCnt[2], classCnt[0] + classCnt[1] + classCnt[2] + classCnt[3] };
+					// the form's rows of the model's table, already in the order the search takes them (ModelView::candRows); the general search and continueChunk read packs
+					const uint4* rows = reinterpret_cast<const uint4*>(candRows + candOff); uint4* dst = reinterpret_cast<uint4*>(packs + pk);
+					uint32_t cnt = 0;
 					for (uint32_t k = 0; k < candCnt; ++k)
 					{
-						const CandStatic o = candStaticOf(M, M.formCand[candOff + k]);
-						const uint32_t flags = o.m1.y & 0xFFFF; const uint8_t tag = (uint8_t)o.m1.z;
-						const uint32_t at = transposed ? classAt[candClassOf(tag, o.m1.z >> 24, flags)]++ : k;
-						packs[pk + at] = o;
-						if (posCandKind(P, flags, tag, spaceBefore)) ++cnt;
+						const uint4 r0 = rows[3 * k], r1 = rows[3 * k + 1], r2 = rows[3 * k + 2];
+						dst[3 * k] = r0; dst[3 * k + 1] = r1; dst[3 * k + 2] = r2;
+						if (posCandKind(P, r1.y & 0xFFFF, (uint8_t)r1.z, spaceBefore)) ++cnt;
 					}
 					if (cnt == 0) atomicOr(&posSlow[e], 1u);      // nothing to evaluate: the reference then retries without conditions and falls back (PathEvaluator.hpp:468-473, 1286-1299)
 					if ((fc & 0x8000u) && rank < 16) atomicOr(&posPass1[e], 1u << rank);
@@ -853,14 +842,14 @@ namespace kamd
 				}
 			}
 			waveSync();
+			LW_MARK(12)
 			for (uint32_t b0 = 0; b0 < G; b0 += 64)
 			{
 				const uint32_t i = b0 + lane;
 				const uint32_t c = i < G ? recOff[i] : 0u;
-				uint32_t incl = c;
-				for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+				const uint32_t incl = waveInclSum(c);
 				if (i < G) recOff[i] = recTop + incl - c;
-				recTop += __shfl(incl, 63);
+				recTop += waveLast(incl);
 			}
 			// the end positions that hold nodes, numbered from 1 (the start node is position 0; the end node is none)
 			for (uint32_t b0 = 0; b0 < nPosAll; b0 += 64)
@@ -912,6 +901,7 @@ namespace kamd
 				}
 			}
 		}
+		LW_MARK(13)
 		auto emitNode = [&](uint32_t ni, uint32_t s, uint32_t t, uint32_t form, uint32_t fc, uint32_t uOff, uint32_t uLen, uint32_t se, uint32_t rankAt, bool isEnd)
 		{
 			DevNode nn;
@@ -1002,7 +992,7 @@ namespace kamd
 			};
 			if (nn.form != NOFORM)
 			{
-				const CandStatic* cl = packs + nn.packOff;      // (this lane's own stores of a moment ago)
+				const CandStatic* cl = candRows + M.forms[form].candOff;      // (the rows phase 8 copied to packs + nn.packOff, from the model's table: no store -> load round trip)
 				const uint32_t of0 = sharedFirstWord(cl, nn.candCnt);
 				for (uint32_t k = 0; k < nn.candCnt; ++k)
 				{
@@ -1079,7 +1069,7 @@ namespace kamd
 			waveSync();
 			if (lane == 0) { if (posOk) desc[0].firstRec = nPos; W.expanded[chunk] = 1; }
 		}
-		LW_MARK(12)
+		LW_MARK(14)
 		if (lane == 0)
 		{
 			const uint32_t packCap = W.packBase[chunk + 1] - W.packBase[chunk];
